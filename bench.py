@@ -11,13 +11,20 @@ One timed step = one optimizer step = GAS micro-batches (forward + backward
 through the native kernels) + bucketed RCCL reduce-scatter (N>1) + fused
 AdamW + bf16 all-gather. Weak scaling: per-GPU work is fixed as N grows.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: either under `python -m torch.distributed.run --nproc-per-node N ...`,
      or plain -- without WORLD_SIZE in the env the script re-launches itself
      as N ranks, kubernetes_cloud_amd/launch.py)
 
-Secondary measurements in the same JSON line (each bounded and fenced off, so
-the headline always prints):
+A plain run does only what the headline needs: set up, W warmup steps, K timed
+steps, the JSON line. ``--dump-outputs DIR`` also writes what the last timed
+step computed (``DIR/loss.npy``: the mean loss ``train_batch`` returned;
+``DIR/params_sample.npy``: a fixed seeded sample of every updated parameter),
+float32, from rank 0; model, token ids and sample positions are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+``--full`` adds the secondary measurements to the same JSON line (each bounded
+and fenced off, so the headline always prints):
 
 * ``secondary``             SD-1.5 txt2img images/s (BASELINE config 5; one
                             replica per GPU, 3 timed batches);
@@ -25,7 +32,7 @@ the headline always prints):
                             (BASELINE config 4);
 * ``allreduce_sweep``       N > 1: custom xGMI one-/two-shot vs RCCL
                             latency by message size (bench/allreduce_bench.py);
-* N = 1 only (``--extra``):
+* N = 1 only (``--full --extra auto|on``):
   ``secondary_dreambooth``  SD-1.5 DreamBooth samples/s (BASELINE config 3,
                             the reference formula: instance batch / step time);
   ``secondary_decode``      GPT-J-6B and GPT-NeoX-20B decode ms/token at batch 1
@@ -65,6 +72,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--model", default="gpt-j-6b")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements (--sd, --bloom-tp, --extra); "
+                         "without it they are skipped whatever those options say")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss.npy, params_sample.npy; float32) to DIR")
     # micro-batch 16 x GAS 2 (global 32): the largest micro-batch that fits 288 GB
     # (peak 216 GiB), as the reference's auto batch size picks the largest that fits
     # (finetuner.py:447-466); vs 8 x 4: 32.7k -> 33.5k tok/s (profiles/bench_gptj_r1_v13_mb16.log)
@@ -91,13 +103,17 @@ def main():
     ap.add_argument("--extra", choices=["auto", "on", "off"], default="auto",
                     help="N=1 secondaries (DreamBooth, GPT-J decode, BLOOM 8-layer slice, weight load); "
                          "'auto' = when N == 1")
-    ap.add_argument("--extra-timeout", type=float, default=600.0,
+    # 500 s: headline + txt2img take under a minute, so a --full run ends within 10 minutes whatever a
+    # secondary does (measured: all five secondaries 390 s, 300 s of them serving)
+    ap.add_argument("--extra-timeout", type=float, default=500.0,
                     help="seconds for all N=1 secondaries together; on overrun the line prints with what finished")
     # rehearsal shrink flags (tests/test_bench_shared_gpu.py): NOT the BASELINE config
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--hidden", type=int, default=0)
     ap.add_argument("--heads", type=int, default=0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the mean over the timed steps)")
 
     # `python bench.py --gpus N` outside torchrun: re-run this script as N ranks
     # (torchrun's env contract) before anything touches the GPU, and exit with
@@ -111,6 +127,8 @@ def main():
               + json.dumps({"world_size": int(os.environ.get("WORLD_SIZE", "1"))}), flush=True)
         return
 
+    if args.full:
+        _private_miopen_db()
     import torch
     import torch.distributed as dist
     from kubernetes_cloud_amd.models.causal_lm import build_model
@@ -204,6 +222,8 @@ def main():
     flops_tok = cfg.flops_per_token(S)
     mfu = tps * flops_tok / (world * 2.5e15)
     loss_v = float(loss.item())
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, eng, model, loss, info.is_main)
     eng.remove_hooks()  # drops the gradient-sink references to the engine
     del eng, model, batches
     torch.cuda.empty_cache()
@@ -240,15 +260,15 @@ def main():
         }
         if shrink or shared:  # rehearsal runs are never a BASELINE measurement
             rec["config"]["rehearsal"] = {"shrink": shrink, "shared_gpu": shared}
-    if args.sd:
+    if args.full and args.sd:
         sd = _sd_txt2img(dev, world, info.is_main)
         if rec is not None:
             rec["secondary"] = sd
-    if args.bloom_tp == "on" or (args.bloom_tp == "auto" and world > 1):
+    if args.full and (args.bloom_tp == "on" or (args.bloom_tp == "auto" and world > 1)):
         bloom = _bloom_tp(args, info, rec)
         if rec is not None:
             rec["bloom_tp"] = bloom
-    if args.extra == "on" or (args.extra == "auto" and world == 1):
+    if args.full and (args.extra == "on" or (args.extra == "auto" and world == 1)):
         _extras(args, dev, rec)
     if rec is not None:
         summ = _summary(rec)
@@ -257,6 +277,45 @@ def main():
         print("[bench] summary " + json.dumps(summ, separators=(",", ":")), file=sys.stderr, flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+def _private_miopen_db():
+    """The SD secondaries run convolutions, and MIOpen appends the find results of shapes it has not
+    seen to its user db, by default the committed tuning/miopen (utils/miopen.py). A benchmark run
+    reads and extends a throw-away copy instead, so it writes nothing into the tree; an explicit
+    MIOPEN_USER_DB_PATH is left alone."""
+    import atexit
+    import shutil
+    import tempfile
+    tuned = os.path.join(ROOT, "tuning", "miopen")
+    if "MIOPEN_USER_DB_PATH" in os.environ or not os.path.isdir(tuned):
+        return
+    db = tempfile.mkdtemp(prefix="kca_miopen_db_")
+    shutil.copytree(tuned, db, dirs_exist_ok=True)
+    os.environ["MIOPEN_USER_DB_PATH"] = db
+    atexit.register(shutil.rmtree, db, ignore_errors=True)
+
+
+def _dump_outputs(out_dir, eng, model, loss, is_main, per_param=4096):
+    """``--dump-outputs``: what the last timed ``train_batch`` handed back -- its mean loss -- and what
+    it left in the model: ``per_param`` elements of every parameter (all of a smaller one) at positions
+    drawn from a generator seeded with 0, in ``named_parameters`` order (~5 MB for GPT-J-6B). Every
+    rank enters (ZeRO gathers are collective); rank 0 writes."""
+    import numpy as np
+    import torch
+    gen = torch.Generator().manual_seed(0)
+    parts = []
+    with eng.gathered(), torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            idx = torch.randint(0, n, (per_param,), generator=gen) if n > per_param else torch.arange(n)
+            if is_main:
+                parts.append(flat[idx.to(flat.device)].float().cpu())
+    if is_main:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+        np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
 
 
 def _summary(rec) -> dict:

@@ -4,6 +4,7 @@ and event payload mappings, and every ``python -m`` entrypoint it names
 exists; the model downloader (local mirror + .ready.txt + tensorize) and the
 ResNet-50 DDP trainer (synthetic data) run."""
 import importlib
+import json
 import os
 import re
 
@@ -13,7 +14,7 @@ import yaml
 
 from kubernetes_cloud_amd.deploy import render, workflows
 
-REF = "/root/reference"
+GOLDEN_PARAMS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workflow_parameter_names.json")
 
 
 def _all_docs(out):
@@ -42,14 +43,12 @@ def test_render_and_gpu_resources(tmp_path):
 
 
 def _ref_params(path):
-    out = []
-    for d in yaml.safe_load_all(open(path)):
-        if d and "spec" in d:
-            out += [p["name"] for p in d["spec"].get("arguments", {}).get("parameters", [])]
-    return out
+    """``spec.arguments.parameters[].name`` of every document of the reference workflow ``path``,
+    as recorded in tests/golden/workflow_parameter_names.json."""
+    with open(GOLDEN_PARAMS) as f:
+        return json.load(f)[path]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
 @pytest.mark.parametrize("ref,ours", [
     ("finetuner-workflow/finetune-workflow.yaml", workflows.FINETUNE_PARAMS),
     ("sd-finetuner-workflow/sd-finetune-workflow-template.yaml", workflows.SD_PARAMS),
@@ -58,7 +57,9 @@ def _ref_params(path):
 ])
 def test_workflow_parameter_surface(ref, ours):
     names = {n for n, _ in ours}
-    missing = [p for p in _ref_params(os.path.join(REF, ref)) if p not in names]
+    params = _ref_params(ref)
+    assert params
+    missing = [p for p in params if p not in names]
     assert not missing, missing
 
 

@@ -14,7 +14,8 @@ from kubernetes_cloud_amd.serving.grpc_v2 import SERVICE, pb, serve
 
 from .helpers import make_model_dir
 
-SAMPLE = "/root/reference/online-inference/fastertransformer/client/sample_request.json"
+# the FT client's sample_request.json, stored with the tests
+SAMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ft_sample_request.json")
 
 
 @pytest.fixture(scope="module")
@@ -34,14 +35,10 @@ def ft_server(tmp_path_factory):
 
 
 def _sample_request(prompt_ids, out_len=8):
-    """sample_request.json's tensors (reference file when present, else its
-    documented values), prompt filled in like example.py's generate_parameters."""
-    if os.path.exists(SAMPLE):
-        fields = json.load(open(SAMPLE))["request"]
-    else:
-        fields = [{"name": "request_output_len", "data": [[64]], "dtype": "int32"},
-                  {"name": "runtime_top_k", "data": [[10]], "dtype": "int32"},
-                  {"name": "random_seed", "data": [[0]], "dtype": "uint64"}]
+    """sample_request.json's tensors (tests/golden/ft_sample_request.json), prompt filled in
+    like example.py's generate_parameters."""
+    with open(SAMPLE) as f:
+        fields = json.load(f)["request"]
     req = pb.ModelInferRequest(model_name="fastertransformer", id="r1")
     for f in fields:
         data = f["data"]

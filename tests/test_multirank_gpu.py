@@ -38,7 +38,7 @@ def _port():
 def test_bench_two_ranks_shared_gpu():
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--layers", "2", "--hidden", "1024", "--heads", "4", "--seq", "512", "--micro-batch", "2", "--gas", "2",
-           "--sd", "0", "--bloom-layers", "2", "--bloom-batches", "1,4", "--bloom-timeout", "240",
+           "--full", "--sd", "0", "--bloom-layers", "2", "--bloom-batches", "1,4", "--bloom-timeout", "240",
            "--tunableop", "off"]
     env = dict(os.environ, KCA_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)

@@ -1,17 +1,20 @@
 """Native BPE (csrc/tokenize/bpe.cpp + data/tokenizer.py) against HF
-``tokenizers`` on the reference's own vocabularies: GPT-2
-(online-inference/fastertransformer/client/gpt_bpe/gpt2-{vocab.json,merges.txt})
-and GPT-NeoX-20B (client/hf_tokenizer/20B_tokenizer.json: NFC normalizer,
-space-run added tokens). Corpus: every markdown/text file of the reference
-tree plus a Unicode stress corpus. Token ids must be identical."""
+``tokenizers`` on the reference's own vocabularies, stored under tests/golden:
+GPT-2 (the FT client's gpt_bpe/gpt2-{vocab.json,merges.txt}, here one gpt2_bpe.json) and GPT-NeoX-20B
+(the client's hf_tokenizer/20B_tokenizer.json: NFC normalizer, space-run added
+tokens). The stored tables are cut to the first 1000 merges, the byte tokens
+and the added tokens, every token with its original id (the full tables are
+megabytes; the cut NeoX vocab also lists the space-run added tokens, which HF
+would otherwise renumber); both implementations load the same cut tables. Corpus: every
+markdown file of this repository and every Python source of the package
+(prose, tables, code) plus a Unicode stress corpus. Token ids must be identical."""
 import glob
 import os
 
 import pytest
 
-REF = "/root/reference"
-GPT2 = os.path.join(REF, "online-inference/fastertransformer/client/gpt_bpe")
-NEOX = os.path.join(REF, "online-inference/fastertransformer/client/hf_tokenizer/20B_tokenizer.json")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 STRESS = [
     "Hello world! It's a test, isn't it? We'll see: you'd've thought they're done.",
@@ -36,12 +39,12 @@ STRESS = [
 
 
 def _corpus():
-    files = sorted(glob.glob(os.path.join(REF, "**", "*.md"), recursive=True)) + \
-        sorted(glob.glob(os.path.join(REF, "**", "*.txt"), recursive=True))
+    files = sorted(glob.glob(os.path.join(ROOT, "*.md"))
+                   + glob.glob(os.path.join(ROOT, "docs", "**", "*.md"), recursive=True)
+                   + glob.glob(os.path.join(ROOT, "profiles", "**", "*.md"), recursive=True)) + \
+        sorted(glob.glob(os.path.join(ROOT, "kubernetes_cloud_amd", "**", "*.py"), recursive=True))
     texts = []
     for f in files:
-        if f.endswith("merges.txt"):
-            continue
         try:
             with open(f, encoding="utf-8") as fh:
                 texts.append(fh.read())
@@ -52,8 +55,6 @@ def _corpus():
 
 @pytest.fixture(scope="module")
 def corpus():
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not mounted")
     return _corpus()
 
 
@@ -68,18 +69,19 @@ def _check(native, ref, corpus):
     assert not bad, bad[:5]
 
 
-def test_gpt2_vocab_parity(corpus):
-    if not os.path.exists(os.path.join(GPT2, "gpt2-vocab.json")):
-        pytest.skip("GPT-2 vocab not present")
-    import shutil
-    import tempfile
+def test_gpt2_vocab_parity(corpus, tmp_path):
+    import json
 
     from tokenizers import AddedToken, Tokenizer, decoders, models, pre_tokenizers
 
     from kubernetes_cloud_amd.data.tokenizer import NativeBPE
-    d = tempfile.mkdtemp()
-    shutil.copy(os.path.join(GPT2, "gpt2-vocab.json"), os.path.join(d, "vocab.json"))
-    shutil.copy(os.path.join(GPT2, "gpt2-merges.txt"), os.path.join(d, "merges.txt"))
+    d = str(tmp_path)
+    with open(os.path.join(GOLDEN, "gpt2_bpe.json"), encoding="utf-8") as f:
+        tables = json.load(f)
+    with open(os.path.join(d, "vocab.json"), "w", encoding="utf-8") as f:
+        json.dump(tables["vocab"], f, ensure_ascii=False)
+    with open(os.path.join(d, "merges.txt"), "w", encoding="utf-8") as f:
+        f.write("\n".join([tables["merges_header"]] + tables["merges"]) + "\n")
     ref = Tokenizer(models.BPE.from_file(os.path.join(d, "vocab.json"), os.path.join(d, "merges.txt")))
     ref.pre_tokenizer = pre_tokenizers.ByteLevel(add_prefix_space=False)
     ref.decoder = decoders.ByteLevel()
@@ -92,12 +94,11 @@ def test_gpt2_vocab_parity(corpus):
 
 
 def test_neox_20b_tokenizer_parity(corpus):
-    if not os.path.exists(NEOX):
-        pytest.skip("20B tokenizer not present")
     from tokenizers import Tokenizer
 
     from kubernetes_cloud_amd.data.tokenizer import NativeBPE
-    ref = Tokenizer.from_file(NEOX)
-    native = NativeBPE(NEOX)
+    neox = os.path.join(GOLDEN, "neox_20b_tokenizer.json")
+    ref = Tokenizer.from_file(neox)
+    native = NativeBPE(neox)
     assert native.normalizer == "NFC" and native.specials["  "] == 50276
     _check(native, ref, corpus)
