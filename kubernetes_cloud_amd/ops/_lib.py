@@ -87,6 +87,9 @@ _SIGS = {
     "kca_skinny_set_smallk": [I],
     "kca_conv3x3_fwd": [P, P, P, P, I, I, I, I, I, P],
     "kca_conv3x3_set_variant": [I],
+    "kca_conv3x3_wflip": [P, P, I, I, P],
+    "kca_conv3x3_wgrad_splits": [I, I, I, I, I],
+    "kca_conv3x3_wgrad": [P, P, P, P, I, I, I, I, I, I, P],
     "kca_skinny_gemm": [P, LL, P, P, P, LL, I, I, I, I, P],
     "kca_skinny_set_splitk": [I],
     "kca_mm_skinny_set": [I],
