@@ -33,6 +33,11 @@ SEGMENTS = {
                     "S=QK^T MFMAs", "mask + softmax", "O+=PV", "epilogue"]),
     "dkdv": (32, ["prologue (K, V image)", "issue Q/dO loads", "S, dP MFMAs", "softmax / dS",
                   "dV, dK MFMAs", "LDS store + barrier", "epilogue (dK, dV stores)"]),
+    # the 8-wave dK/dV kernel (variant bit 1): its dV half (waves 0-3) and its dK half (waves 4-7)
+    "dkdv_w8": (40, ["prologue (K)", "issue Q/dO loads", "S MFMAs", "softmax, P -> LDS", "dV MFMAs",
+                     "LDS store + barrier", "epilogue (dV stores)"]),
+    "dkdv_w8_k": (56, ["prologue (V)", "step head", "dP MFMAs", "issue Q/dO loads, P <- LDS, dS", "dK MFMAs",
+                       "LDS store + barrier", "epilogue (dK stores)"]),
 }
 
 
@@ -40,7 +45,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="gptj")
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--variant", type=int, default=-1, help="kca_attn_set_variant bits; -1 = default")
+    ap.add_argument("--kernel", default="", help="only this kernel's segments (dkdv_w8: both halves)")
     a = ap.parse_args()
+    if a.kernel == "dkdv_w8" and a.variant < 0:
+        a.variant = 3
+    if a.variant >= 0:
+        ops.attention.set_variant(a.variant)
     from attn_bench import SHAPES  # noqa: E402  (bench/ is this script's directory)
     B, Sq, Sk, H, D, causal = SHAPES[a.shape]
     lib = _lib.require()
@@ -64,6 +75,8 @@ def main():
     vals = list(buf)
     out = {"shape": a.shape, "B": B, "S": Sq, "H": H, "D": D, "causal": causal, "iters": a.iters}
     for kern, (base, names) in SEGMENTS.items():
+        if a.kernel and not kern.startswith(a.kernel):
+            continue
         seg = vals[base:base + len(names)]
         waves = vals[base + 7]
         tot = sum(seg) or 1

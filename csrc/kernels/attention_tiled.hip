@@ -32,7 +32,8 @@ constexpr float kRescaleThr = 8.0f;
 
 // Diagnostic build only (-DKCA_ATTN_STAMPS, bench/attn_stamps.py): per-wave s_memtime segment
 // sums of the main loops, added into g_attn_stamps once per wave at the end (fwd slots 0..7,
-// dQ 16..23, dK/dV 32..39). The fences around each stamp forbid overlaps the real kernel has: read
+// dQ 16..23, dK/dV 32..39, 8-wave forward 48..55, 8-wave dK/dV 40..47 (dV half) and 56..63 (dK
+// half)). The fences around each stamp forbid overlaps the real kernel has: read
 // the shares, not the lengths. In the normal build every ASTAMP is empty.
 #ifdef KCA_ATTN_STAMPS
 __device__ unsigned long long g_attn_stamps[64];
@@ -114,19 +115,21 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t head_rsrc(const bf16_t* b) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)au, (short)0, 0x7fffffff, 0x00020000);
 }
 
-// Staging of a 32-row x D tile by the 256 threads of a workgroup: chunk idx = tid + 256*i is
-// (row idx / NCH, 16-B chunk idx % NCH). D = 96 / 160 serve SD-1.5's 80-wide heads (padded to
-// 96) and its 160-wide heads (native) instead of padding them to 128 / 256.
-template <int D, bool POW2 = (256 % (D / 8)) == 0>
+// Staging of a 32-row x D tile by the NT (256; 512 in the 8-wave dK/dV kernel) threads of a
+// workgroup: chunk idx = tid + NT*i is (row idx / NCH, 16-B chunk idx % NCH). D = 96 / 160 serve
+// SD-1.5's 80-wide heads (padded to 96) and its 160-wide heads (native) instead of padding them
+// to 128 / 256.
+template <int D, bool POW2 = (256 % (D / 8)) == 0, int NT = 256>
 struct Stager;
 
 // D = 64 / 128 / 256: thread tid owns chunk column tid % NCH of rows tid / NCH + i * RPI.
 // Loads go through buffer resources (T8): the per-thread byte offsets are loop constants in
 // VGPRs and the tile's row offset k0 * stride is ONE scalar -- no 64-bit address arithmetic on the
 // VALU per load, which at D = 64 (SD-1.5's padded heads) is VALU-issue-bound.
-template <int D>
-struct Stager<D, true> {
-  static constexpr int NCH = D / 8, CPT = 32 * NCH / 256, RPI = 256 / NCH;
+template <int D, int NT>
+struct Stager<D, true, NT> {
+  static constexpr int NCH = D / 8, CPT = 32 * NCH / NT, RPI = NT / NCH;
+  static_assert(CPT >= 1 && NT % NCH == 0, "stager: at least one chunk per thread");
   long long ok_, ov_;  // element offset of this thread's first chunk in a K / V tile
   int row0_, ch_;
   __amdgpu_buffer_rsrc_t rk_, rv_;
@@ -158,16 +161,27 @@ struct Stager<D, true> {
     const int sov = __builtin_amdgcn_readfirstlane((int)(k0 * v_st * 2));
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
-      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rk_, vok_[i], sok, 0);
-      const auto b = __builtin_amdgcn_raw_buffer_load_b128(rv_, vov_[i], sov, 0);
-      sk[i] = *reinterpret_cast<const u32x4*>(&a);
-      sv[i] = *reinterpret_cast<const u32x4*>(&b);
+      if constexpr (NT == 256) {
+        const auto a = __builtin_amdgcn_raw_buffer_load_b128(rk_, vok_[i], sok, 0);
+        const auto b = __builtin_amdgcn_raw_buffer_load_b128(rv_, vov_[i], sov, 0);
+        sk[i] = *reinterpret_cast<const u32x4*>(&a);
+        sv[i] = *reinterpret_cast<const u32x4*>(&b);
+      } else {  // the 8-wave kernel is register-bound: chunk i's row offset rides in the scalar offset
+        const int sk_i = __builtin_amdgcn_readfirstlane((int)((k0 + i * RPI) * k_st * 2));
+        const int sv_i = __builtin_amdgcn_readfirstlane((int)((k0 + i * RPI) * v_st * 2));
+        const auto a = __builtin_amdgcn_raw_buffer_load_b128(rk_, vok_[0], sk_i, 0);
+        const auto b = __builtin_amdgcn_raw_buffer_load_b128(rv_, vov_[0], sv_i, 0);
+        sk[i] = *reinterpret_cast<const u32x4*>(&a);
+        sv[i] = *reinterpret_cast<const u32x4*>(&b);
+      }
     }
   }
   __device__ __forceinline__ void store(const u32x4 (&sk)[CPT], const u32x4 (&sv)[CPT], char* buf) const {
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
-      const int o = img_off<D>(row0_ + i * RPI, ch_);
+      // RPI a multiple of 16 rows: a constant image offset (an `or` would hide it from the DS offset field)
+      const int o = (NT != 256 && RPI % 16 == 0) ? img_off<D>(row0_, ch_) + i * (RPI / 8) * 16 * D
+                                                : img_off<D>(row0_ + i * RPI, ch_);
       *reinterpret_cast<u32x4*>(buf + o) = sk[i];
       *reinterpret_cast<u32x4*>(buf + 32 * D * 2 + o) = sv[i];
     }
@@ -178,7 +192,7 @@ struct Stager<D, true> {
 // the first (32 * NCH) % 256 threads (whole waves) and each i has its own (row, chunk), with the
 // element offsets precomputed once, outside the key loop
 template <int D>
-struct Stager<D, false> {
+struct Stager<D, false, 256> {
   static constexpr int NCH = D / 8, TOT = 32 * NCH, CPT = (TOT + 255) / 256;
   static_assert(D % 32 == 0 && TOT % 64 == 0, "tiled attention: D multiple of 32");
   long long ok_[CPT], ov_[CPT];
@@ -846,6 +860,8 @@ __global__ void __launch_bounds__(NW * 64, 1) attn_fwd_w8_kernel(FastFwdParams p
 //                tiles (and the query heads of its KV head for GQA).
 //                S = Q.K^T, dP = dO.V^T (key on the lane), dV^T += dO^T.P,
 //                dK^T += Q^T.dS with dO^T, Q^T by transposed reads.
+//                D = 256, H == Hkv: attn_bwd_dkdv_w8_kernel, the same products split
+//                over a pair of waves per 32 keys (two waves per SIMD).
 struct FastBwdParams {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* dout;
   bf16_t* dq; bf16_t* dk; bf16_t* dv;
@@ -1262,16 +1278,296 @@ __global__ void __launch_bounds__(256, (D <= 64 && !CAUSAL) ? 3 : 1) attn_bwd_dk
   ASTAMP_FLUSH(32);
 }
 
+// D = 256 dK/dV at two waves per SIMD (A/B bit 1 of g_attn_variant; H == Hkv only, GQA keeps the
+// kernel above). The 4-wave kernel holds dK^T and dV^T -- 256 accumulator registers -- in one wave,
+// so nothing on its SIMD covers the exp / dS VALU block, the LDS round trips at the head of each
+// MFMA group, the staging store and the barrier. Here the 32 keys of a wave belong to a PAIR of
+// waves (w, w + 4: the same SIMD) that split the two accumulators:
+//   "V wave" w + 4: K fragments in registers; S = Q.K^T, P = exp2(..) (mask), dV^T += dO^T.P;
+//                   hands P to its partner as fp32 through a 4 KB LDS buffer.
+//   "K wave" w    : V fragments in registers; dP = dO.V^T, dS = P (dP - delta), dK^T += Q^T.dS.
+// Each wave: 128 accumulators, 32 of the tile's 64 MFMAs. The K wave runs ONE tile behind the V
+// wave, so the P it needs was published by the previous step's barrier: one barrier per step,
+// reached by all eight waves total + 1 times, no flags, no atomics. The skew costs a third Q/dO
+// buffer and a second P buffer; K and V in registers free the four V images.
+// The MFMA shapes, the fp32 P, the dS expression and the accumulation order over the Q tiles are
+// the 4-wave kernel's: dK and dV come out bit-identical to it.
+// LDS per tile step and pair: Q rows 16 KB + dO^T 16 KB + P 4 KB written (V wave), dO rows 16 KB +
+// Q^T 16 KB + P 4 KB read (K wave) = 72 KB; per workgroup 288 KB + the 32 KB staging store.
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(512, 1) attn_bwd_dkdv_w8_kernel(FastBwdParams p) {
+  constexpr int BK = 128, BQ = 32;
+  constexpr int TILE = BQ * D * 2;            // one 32-row image
+  using Stg = Stager<D, true, 512>;
+  constexpr int CPT = Stg::CPT, KSD = D / 16;
+  constexpr int PSZ = 4 * 64 * 16;            // P of one pair: [g 4][lane 64] f32x4
+  constexpr int POFF = 3 * 2 * TILE;          // P exchange: [buf 2][pair 4]
+  constexpr int LOFF = POFF + 2 * 4 * PSZ;    // lse/delta: [buf 3][64] floats
+  __shared__ __attribute__((aligned(16))) char smem[LOFF + 3 * 64 * 4];
+  static_assert(8 * 32 * D * 2 <= LOFF, "epilogue images of the 8 waves");
+  ASTAMP_DECL
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int pw = wave & 3;          // the pair: 32 keys
+  const bool kside = wave < 4;      // K wave (dK) / V wave (dV)
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int nkb = p.Sk / BK;
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int kb = lid % nkb, bh = lid / nkb;
+  const int b = bh / p.H, h = bh % p.H;
+  const int off = p.Sk - p.Sq;
+  const int kw = kb * BK + pw * 32;
+  const int key = kw + l32;
+  const float sl2 = p.scale * kLog2e;
+
+  // the resident B operand: this lane's K row (V wave) or V row (K wave), chunk 2s + hh per k-step
+  bf16x8 rf[KSD];
+  {
+    const bf16_t* rp = kside ? p.v + b * p.v_sb + h * p.v_sh + (long long)key * p.v_st
+                             : p.k + b * p.k_sb + h * p.k_sh + (long long)key * p.k_st;
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) rf[s] = *reinterpret_cast<const bf16x8*>(rp + 16 * s + 8 * hh);
+  }
+  f32x16 acc[D / 32];  // dV^T (V wave) / dK^T (K wave)
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+  int q_lo = 0;
+  if (CAUSAL) q_lo = max(0, kb * BK - off) & ~(BQ - 1);
+  const int total = (p.Sq - q_lo) / BQ;
+
+  const bf16_t* qb = p.q + b * p.q_sb + h * p.q_sh;
+  const bf16_t* gb = p.dout + b * p.do_sb + h * p.do_sh;
+  Stg stg(tid, p.q_st, p.do_st);
+  stg.bind(qb, gb, p.q_st, p.do_st);
+  u32x4 sq[CPT], sg[CPT];
+  float lreg = 0.f;
+  int be, bo, b1, b2;
+  row_bases<D>(l32, hh, be, bo);
+  tr_bases<D>(lane, b1, b2);
+
+  // lse * log2e (wave 4, for the V waves) / delta (wave 0, for the K waves): one uniform source per
+  // wave, scaled at the LDS store so that no step waits on the load it has just issued
+  const float* lsrc = (kside ? p.delta : p.lse) + ((long long)b * p.H + h) * p.Sq + q_lo;
+  const float lmul = kside ? 1.f : kLog2e;
+  const bool lwave = pw == 0 && lane < 32;
+  // tile it -> registers (each half its 256 threads' chunks)
+  auto load_tile = [&](int it) {
+    stg.load(sq, sg, qb, gb, q_lo + it * BQ, p.q_st, p.do_st);
+    if (lwave) lreg = lsrc[it * BQ + lane];
+  };
+  auto store_tile = [&](int buf) {
+    stg.store(sq, sg, smem + buf * 2 * TILE);
+    if (lwave) reinterpret_cast<float*>(smem + LOFF)[buf * 64 + (kside ? 32 : 0) + lane] = lreg * lmul;
+  };
+
+  if (total > 0) {
+    load_tile(0);
+    store_tile(0);
+  }
+  __syncthreads();
+  ASTAMP(0);
+
+  // Step s: the V waves work on tile s (buffer s % 3), the K waves on tile s - 1, and all 512
+  // threads stage tile s + 1 into buffer (s + 1) % 3, last read in step s - 1. P of tile s sits in
+  // P buffer s & 1, last read (tile s - 2) in step s - 1.
+  // As in the 4-wave kernel: the (at most 3 per head) q tiles wholly above a pair's keys are
+  // masked to P = 0, not skipped, and the mask is applied on every tile.
+  // The second-dispatched half loses every issue arbitration at equal priority, and the V waves carry
+  // the longer VALU block (exp2, mask, two conversions): they are that half, at priority 1 throughout.
+  if (!kside) {
+    __builtin_amdgcn_s_setprio(1);
+    auto v_step = [&](int t, int cur, int nxt) {
+      const char* Qs = smem + cur * 2 * TILE;
+      const char* Gs = Qs + TILE;
+      const float* ls = reinterpret_cast<const float*>(smem + LOFF) + cur * 64;
+      float* pb = reinterpret_cast<float*>(smem + POFF + ((t & 1) * 4 + pw) * PSZ);
+      const int qt = q_lo + t * BQ;
+      load_tile(min(t + 1, total - 1));
+      asm volatile("" ::: "memory");
+      ASTAMP(1);
+      f32x16 sacc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+      // S = Q.K^T with the LDS fragment of k-step s+PF requested before the MFMA of step s
+      {
+        constexpr int PF = 1;
+        bf16x8 f[PF + 1];
+#pragma unroll
+        for (int s = 0; s < PF; ++s) f[s] = row_frag<D>(Qs, be, bo, s);
+        __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
+#pragma unroll
+        for (int s = 0; s < KSD; ++s) {
+          if (s + PF < KSD) {
+            f[(s + PF) % (PF + 1)] = row_frag<D>(Qs, be, bo, s + PF);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s % (PF + 1)], rf[s], sacc, 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        }
+      }
+      ASTAMP(2);
+      // rows q = qt + 8g + 4hh + j (g = r>>2, j = r&3); visible iff key <= q + off
+      const int lim = key - qt - off - 4 * hh;
+      bf16x8 p0, p1;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 lq = *reinterpret_cast<const f32x4*>(ls + 8 * g + 4 * hh);
+        f32x4 pg;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * g + j;
+          float pr = __builtin_amdgcn_exp2f(fmaf(sacc[r], sl2, -lq[j]));
+          if constexpr (CAUSAL) {
+            if (8 * g + j < lim) pr = 0.f;
+          }
+          pg[j] = pr;
+          if (r < 8) p0[r] = (__bf16)pr;
+          else p1[r - 8] = (__bf16)pr;
+        }
+        *reinterpret_cast<f32x4*>(pb + (g * 64 + lane) * 4) = pg;  // fp32 P for the K wave
+      }
+      ASTAMP(3);
+      // dV^T += dO^T.P: fragment i = 2 db + s in f[i % 3], read two MFMAs ahead of its use
+      {
+        bf16x8 f[3];
+        f[0] = tr_frag<D>(Gs, b1, b2, 0, 0);
+        f[1] = tr_frag<D>(Gs, b1, b2, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+        for (int i = 0; i < D / 16; ++i) {
+          if (i + 2 < D / 16) {
+            f[(i + 2) % 3] = tr_frag<D>(Gs, b1, b2, i & 1, (i + 2) >> 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          }
+          acc[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[i % 3], (i & 1) ? p1 : p0, acc[i >> 1], 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        }
+      }
+      ASTAMP(4);
+      asm volatile("" ::: "memory");
+      if (t + 1 < total) store_tile(nxt);
+      __syncthreads();
+      ASTAMP(5);
+    };
+    int cur = 0;
+    for (int t = 0; t < total; ++t) {
+      const int nxt = cur == 2 ? 0 : cur + 1;
+      v_step(t, cur, nxt);
+      cur = nxt;
+    }
+    __syncthreads();  // step `total`: the K waves' last tile
+  } else {
+    auto k_step = [&](int t, int cur, int nxt) {  // in step t + 1; nxt: buffer of tile t + 2
+      const char* Qs = smem + cur * 2 * TILE;
+      const char* Gs = Qs + TILE;
+      const float* ls = reinterpret_cast<const float*>(smem + LOFF) + cur * 64 + 32;
+      const float* pb = reinterpret_cast<const float*>(smem + POFF + ((t & 1) * 4 + pw) * PSZ);
+      ASTAMP(1);
+      f32x16 dpacc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dpacc[r] = 0.f;
+      // dP = dO.V^T, same pinning
+      {
+        constexpr int PF = 1;
+        bf16x8 f[PF + 1];
+#pragma unroll
+        for (int s = 0; s < PF; ++s) f[s] = row_frag<D>(Gs, be, bo, s);
+        __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
+#pragma unroll
+        for (int s = 0; s < KSD; ++s) {
+          if (s + PF < KSD) {
+            f[(s + PF) % (PF + 1)] = row_frag<D>(Gs, be, bo, s + PF);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+          dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s % (PF + 1)], rf[s], dpacc, 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        }
+      }
+      ASTAMP(2);
+      // this half's global loads go out here, not at the head of the step beside the V waves': eight
+      // waves issuing 32 KB at once held every wave's issue for ~500 cycles (stamps)
+      load_tile(min(t + 2, total - 1));
+      asm volatile("" ::: "memory");
+      bf16x8 s0, s1;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 pg = *reinterpret_cast<const f32x4*>(pb + (g * 64 + lane) * 4);
+        const f32x4 dq4 = *reinterpret_cast<const f32x4*>(ls + 8 * g + 4 * hh);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * g + j;
+          const float ds = pg[j] * (dpacc[r] - dq4[j]);
+          if (r < 8) s0[r] = (__bf16)ds;
+          else s1[r - 8] = (__bf16)ds;
+        }
+      }
+      ASTAMP(3);
+      // dK^T += Q^T.dS, same rotation
+      {
+        bf16x8 f[3];
+        f[0] = tr_frag<D>(Qs, b1, b2, 0, 0);
+        f[1] = tr_frag<D>(Qs, b1, b2, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+        for (int i = 0; i < D / 16; ++i) {
+          if (i + 2 < D / 16) {
+            f[(i + 2) % 3] = tr_frag<D>(Qs, b1, b2, i & 1, (i + 2) >> 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          }
+          acc[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[i % 3], (i & 1) ? s1 : s0, acc[i >> 1], 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        }
+      }
+      ASTAMP(4);
+      asm volatile("" ::: "memory");
+      if (t + 2 < total) store_tile(nxt);
+      __syncthreads();
+      ASTAMP(5);
+    };
+    // step 0: no P yet -- only this half's share of tile 1
+    if (total > 1) {
+      load_tile(1);
+      store_tile(1);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < total; ++t) {
+      const int nxt = cur == 0 ? 2 : cur - 1;  // (cur + 2) % 3
+      k_step(t, cur, nxt);
+      cur = cur == 2 ? 0 : cur + 1;
+    }
+  }
+  __builtin_amdgcn_s_setprio(0);
+  // all LDS reads are behind the last barrier: the buffers become the 8 epilogue images
+  {
+    bf16_t* dst = kside ? p.dk + b * p.dk_sb + h * p.dk_sh + (long long)kw * p.dk_st
+                        : p.dv + b * p.dv_sb + h * p.dv_sh + (long long)kw * p.dv_st;
+    store_tile_lds<D>(dst, kside ? p.dk_st : p.dv_st, acc, lane, kside ? p.scale : 1.f, smem + wave * 32 * D * 2);
+  }
+  ASTAMP(6);
+  if (!kside) {
+    ASTAMP_FLUSH(40);
+  } else {
+    ASTAMP_FLUSH(56);
+  }
+}
+
 // the staged K/V (dK/dV: Q/dO) rows are addressed as 32-bit byte offsets from a
 // per-head buffer resource; longer rows fall back to the generic kernel
 inline bool offsets_fit(long long rows, long long stride) { return (rows + 128) * stride * 2 < (1ll << 31); }
 
 }  // namespace
 
-// A/B knob for the full-tile kernels: bit 0 = 8-wave D = 256 forward (attn_fwd_w8_kernel).
+// A/B knob for the full-tile kernels: bit 0 = 8-wave D = 256 forward (attn_fwd_w8_kernel),
+// bit 1 = 8-wave (two waves per SIMD) D = 256 dK/dV (attn_bwd_dkdv_w8_kernel; H == Hkv).
 // (An LDS-DMA dQ kernel -- four buffers, three K/V tiles in flight, asm LDS reads -- measured
 // 1.5-2.5 % slower on GPT-J fwd+bwd than the register-staged one and was dropped.)
-static int g_attn_variant = 1;
+// Both on by default (bit 1: GPT-J step 1910 -> 1879 ms same box, profiles/attn_dkdv_w8_ab_r7.jsonl).
+static int g_attn_variant = 3;
 KCA_API int kca_attn_set_variant(int v) {
   g_attn_variant = v;
   return 0;
@@ -1371,11 +1667,15 @@ KCA_API int kca_attn_bwd_tiled(const void* q, const void* k, const void* v, cons
     hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<64, false, 48>), g1, dim3(256), 0, stream, p);
     hipLaunchKernelGGL((attn_bwd_dq_tiled_kernel<64, false, 48>), g2, dim3(256), 0, stream, p);
   } else if (d == 256) {
+    // the 8-wave dK/dV kernel has no sweep over the query heads of a KV head: GQA keeps the 4-wave one
+    const bool w8 = (g_attn_variant & 2) && H == Hkv;
     if (causal) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<256, true>), g1, dim3(256), 0, stream, p);
+      if (w8) hipLaunchKernelGGL((attn_bwd_dkdv_w8_kernel<256, true>), g1, dim3(512), 0, stream, p);
+      else hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<256, true>), g1, dim3(256), 0, stream, p);
       hipLaunchKernelGGL((attn_bwd_dq_tiled_kernel<256, true>), g2, dim3(256), 0, stream, p);
     } else {
-      hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<256, false>), g1, dim3(256), 0, stream, p);
+      if (w8) hipLaunchKernelGGL((attn_bwd_dkdv_w8_kernel<256, false>), g1, dim3(512), 0, stream, p);
+      else hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<256, false>), g1, dim3(256), 0, stream, p);
       hipLaunchKernelGGL((attn_bwd_dq_tiled_kernel<256, false>), g2, dim3(256), 0, stream, p);
     }
   } else if (d == 160) {

@@ -26,6 +26,7 @@ DEBUG = os.environ.get("KCA_DEBUG", "0") in ("1", "true")
 KERNEL_LIB = os.path.join(LIB_DIR, "libkca_kernels_debug.so" if DEBUG else "libkca_kernels.so")
 # KCA_KERNEL_LIB=<path>: load another build of the kernel library (same-box A/B of a kernel change)
 KERNEL_LIB = os.environ.get("KCA_KERNEL_LIB") or KERNEL_LIB
+ATTN_VARIANT_ENV = os.environ.get("KCA_ATTN_VARIANT")
 
 _lock = threading.Lock()
 _lib = None
@@ -148,6 +149,10 @@ def _load():
                 continue
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
+        # KCA_ATTN_VARIANT=<bits>: the attention kernels' A/B knob (ops/attention.py set_variant), read
+        # once here so a whole program (bench.py) can be A/B-ed from its environment
+        if ATTN_VARIANT_ENV is not None and hasattr(lib, "kca_attn_set_variant"):
+            lib.kca_attn_set_variant(int(ATTN_VARIANT_ENV))
         _lib = lib
         return _lib
 

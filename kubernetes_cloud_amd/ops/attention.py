@@ -71,12 +71,17 @@ def set_tiled_path(enable: bool) -> None:
     _lib.call("kca_attn_set_tiled", int(bool(enable)))
 
 
-_VARIANT = [1]
+# the library's built-in default (g_attn_variant, attention_tiled.hip), or KCA_ATTN_VARIANT, which
+# ops/_lib.py hands to the library once when it loads it
+DEFAULT_VARIANT = 3
+_VARIANT = [int(_lib.ATTN_VARIANT_ENV) if _lib.ATTN_VARIANT_ENV is not None else DEFAULT_VARIANT]
 
 
 def set_variant(v: int) -> int:
     """Full-tile kernel variants (A/B knob, attention_tiled.hip): bit 0 = the 8-wave D = 256
-    forward (default on). Returns the previous value."""
+    forward (default on); bit 1 = the 8-wave, two-waves-per-SIMD D = 256 dK/dV kernel
+    (attn_bwd_dkdv_w8_kernel; H == Hkv, GQA keeps the 4-wave kernel). The environment variable
+    KCA_ATTN_VARIANT sets the initial value. Returns the previous value."""
     _lib.call("kca_attn_set_variant", int(v))
     old, _VARIANT[0] = _VARIANT[0], int(v)
     return old

@@ -36,6 +36,7 @@ CASE_OF = [
     (r"attn_fwd_w8_kernel<256", "attn_gptj", "fwd_flops", None),
     (r"attn_bwd_dq_tiled_kernel<256", "attn_gptj", "bwd_flops_dq", None),
     (r"attn_bwd_dkdv_tiled_kernel<256", "attn_gptj", "bwd_flops_dkdv", None),
+    (r"attn_bwd_dkdv_w8_kernel<256", "attn_gptj", "bwd_flops_dkdv", None),
     (r"attn_fwd_tiled_kernel<64, false, -1, 48", "attn_sd_tiled48", "fwd_flops", None),
     (r"attn_bwd_dq_tiled_kernel<64, false, 48", "attn_sd_tiled48", "bwd_flops_dq", None),
     (r"attn_bwd_dkdv_tiled_kernel<64, false, 48", "attn_sd_tiled48", "bwd_flops_dkdv", None),
