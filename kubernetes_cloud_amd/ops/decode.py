@@ -246,7 +246,7 @@ def gemv_dual_ln(x1: torch.Tensor, w1: torch.Tensor, x2: torch.Tensor | None, w2
 
 
 def gemv_dual_ln_reference(x1, w1, x2, w2, bias, h, gamma, beta, eps):
-    """fp32 reference of ``gemv_dual_ln``: (h + y rounded to bf16, LayerNorm of it)."""
+    """fp32 reference of ``gemv_dual_ln``: (h + y rounded to ``h.dtype``, LayerNorm of it)."""
     y = x1.float() @ w1.float().t()
     if x2 is not None:
         y = y + x2.float() @ w2.float().t()

@@ -48,7 +48,8 @@ _SKINNY_MAX_M = int(os.environ.get("KCA_SKINNY_MAX_M", "2"))
 
 def skinny_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, act: int = 0,
                   out: torch.Tensor | None = None) -> torch.Tensor:
-    """x [M, K] (row stride multiple of 8), weight [N, K] contiguous."""
+    """x [M, K] (unit column stride, row stride multiple of 8), weight [N, K] contiguous, bias contiguous;
+    anything else takes the ``F.linear`` path."""
     M, K = x.shape
     N = weight.shape[0]
     # measured on MI355X (profiles/gemv_bench_r1.jsonl, decode_bench in context): the skinny kernel wins
@@ -59,8 +60,10 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | No
     # M = 2 takes the register-resident K-split form only for K <= 8192 (GPT-J); BLOOM's K = 14336
     # QKV / fc_in at M = 2 would fall to the row-per-wave kernel, which hipBLASLt beats on big weights
     regs = M == 1 or K <= 8192 or small
-    if M == 1 and _lib.native_f16(x, weight) and K % 8 == 0 and weight.is_contiguous() \
-            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0 and (bias is None or bias.dtype == x.dtype):
+    bias_ok = bias is None or bias.is_contiguous()  # the kernels take bias.data_ptr() alone
+    if M == 1 and _lib.native_f16(x, weight) and K % 8 == 0 and x.stride(1) == 1 and weight.is_contiguous() \
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0 and (bias is None or bias.dtype == x.dtype) \
+            and bias_ok:
         # fp16 (FT / DS-Inference serving precision): the single-row GEMV's fp16 instantiation
         if out is None:
             out = torch.empty(M, N, device=x.device, dtype=x.dtype)
@@ -71,7 +74,7 @@ def skinny_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | No
             and x.stride(1) == 1
             and x.stride(0) % 8 == 0
             and weight.is_contiguous() and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
-            and (bias is None or bias.dtype == torch.bfloat16)):
+            and (bias is None or bias.dtype == torch.bfloat16) and bias_ok):
         _set_mode()
         if out is None:
             out = torch.empty(M, N, device=x.device, dtype=x.dtype)

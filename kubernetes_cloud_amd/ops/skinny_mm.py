@@ -15,6 +15,17 @@ re-read from L2, and the epilogues / prologues of a decode layer are folded in:
 bf16 and fp16 (the precision FT / DS-Inference serve, BASELINE config 4). The descriptor is a
 ``ctypes.Structure`` mirroring ``MmArgs``; the entry point copies it into the kernel arguments, so a
 launch is graph-capturable like any other.
+
+Split-K workspace contract (``_workspace``): a K-split launch is handed a ``(ws, bcnt)`` pair -- fp32
+partial tiles and per-block arrival counters that must read zero when the kernel starts (the last
+arriver re-arms them). A captured graph keeps the pair's addresses for as long as it is replayed, so
+
+* a pair that any launch has been handed is never freed while the module lives: an outgrown pair stays
+  in its stream's list and the next one is at least twice as large, which keeps that list short;
+* a graph's replay never relies on another graph (or on eager work) for the zeroed counters: the first
+  launch of every capture that uses a pair records a memset of that pair's counters in its own graph,
+  and the first eager launch that meets a pair allocated inside a capture zeroes it for real;
+* launches on two streams never share a pair (one list per (device, stream)).
 """
 from __future__ import annotations
 
@@ -56,8 +67,9 @@ _KS = int(os.environ.get("KCA_MM_KS", "0"))
 _NR = int(os.environ.get("KCA_MM_NR", "1"))
 _KC = int(os.environ.get("KCA_MM_KC", "0"))  # K per chunk 128 / 256
 _WV = int(os.environ.get("KCA_MM_WV", "0"))  # waves per workgroup 4 / 8
-# split-K workspaces (fp32 partial tiles + zeroed per-block arrival counters), one per (device, stream):
-# launches on one stream are ordered, launches on two streams must not share the counters
+# split-K workspaces (fp32 partial tiles + zeroed per-block arrival counters), per (device, stream):
+# launches on one stream are ordered, launches on two streams must not share the counters. Every
+# pair ever handed out stays in its list, the current one last (module docstring)
 _WS: dict = {}
 _ABI_OK = None
 
@@ -176,15 +188,56 @@ def job(parts, N: int, y: torch.Tensor, bias=None, act: int = 0, res=None, stats
     return j
 
 
+class _Pair:
+    """One workspace: ``zeroed`` is True once the counters were zeroed by eager work (they then stay
+    zero between launches for every later user), else the ids of the captures whose graphs zero them."""
+    __slots__ = ("ws", "bcnt", "zeroed")
+
+    def __init__(self, ws, bcnt, zeroed):
+        self.ws, self.bcnt, self.zeroed = ws, bcnt, zeroed
+
+
+_NEW_CAPTURE = [0]
+
+
+def _capture_id(device, stream: int) -> int:
+    """0 when ``stream`` is not capturing, else a nonzero id of the running capture: the HIP runtime's
+    (``hipStreamGetCaptureInfo``, reached through the kernel library's runtime dependency), or a fresh
+    one per call where that query is unavailable -- every launch of a capture then zeroes its counters."""
+    if torch.device(device).type != "cuda" or not torch.cuda.is_current_stream_capturing():
+        return 0
+    fn = getattr(_lib.require(), "hipStreamGetCaptureInfo", None)
+    if fn is not None:
+        status, cid = ctypes.c_int(0), ctypes.c_ulonglong(0)
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        if fn(stream, ctypes.addressof(status), ctypes.addressof(cid)) == 0 and status.value == 1 and cid.value:
+            return cid.value
+    _NEW_CAPTURE[0] -= 1
+    return _NEW_CAPTURE[0]
+
+
 def _workspace(device, floats: int, nblk: int):
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    ws = _WS.get(key)
-    if ws is None or ws[0].numel() < floats or ws[1].numel() < nblk:
-        f = max(floats, ws[0].numel() if ws else 0, 1 << 20)
-        n = max(nblk, ws[1].numel() if ws else 0, 4096)
-        ws = (torch.empty(f, device=device, dtype=torch.float32), torch.zeros(n, device=device, dtype=torch.int32))
-        _WS[key] = ws
-    return ws
+    """The (ws, bcnt) tensors of a K-split launch on the current stream (module docstring: never freed,
+    counters zeroed within the running capture)."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    pairs = _WS.setdefault((str(device), stream), [])
+    cid = _capture_id(device, stream)
+    p = pairs[-1] if pairs else None
+    if p is None or p.ws.numel() < floats or p.bcnt.numel() < nblk:
+        f = max(floats, 2 * p.ws.numel() if p else 0, 1 << 20)
+        n = max(nblk, 2 * p.bcnt.numel() if p else 0, 4096)
+        # (inside a capture the zero fill is a memset node of that graph only)
+        p = _Pair(torch.empty(f, device=device, dtype=torch.float32),
+                  torch.zeros(n, device=device, dtype=torch.int32), {cid} if cid else True)
+        pairs.append(p)
+    elif p.zeroed is not True and cid not in p.zeroed:
+        p.bcnt.zero_()
+        if cid:
+            p.zeroed.add(cid)
+        else:
+            p.zeroed = True
+    return p.ws, p.bcnt
 
 
 def plan(jobs, M: int, dtype: torch.dtype, ks: int | None = None, nr: int | None = None):

@@ -17,12 +17,12 @@ def _cl(t):
 @pytest.mark.parametrize("N,H,W,C,Co,bias", [(2, 8, 8, 64, 64, False), (1, 16, 8, 128, 192, True),
                                              (3, 8, 16, 64, 320, True), (2, 32, 32, 320, 320, False),
                                              (1, 16, 16, 640, 1280, True)])
-def test_conv3x3_matches_fp32(N, H, W, C, Co, bias):
+def test_conv3x3_matches_fp32(N, H, W, C, Co, bias, monkeypatch):
     from kubernetes_cloud_amd.ops import _lib
     from kubernetes_cloud_amd.ops import conv as kconv
     from kubernetes_cloud_amd.ops.conv import conv3x3, conv3x3_reference, supported
     _lib.require()
-    kconv._MODE = "all"
+    monkeypatch.setattr(kconv, "_MODE", "all")
     g = torch.Generator(device=dev).manual_seed(N * 1000 + C + Co)
     x = _cl(torch.randn(N, C, H, W, device=dev, generator=g).bfloat16())
     w = _cl((torch.randn(Co, C, 3, 3, device=dev, generator=g) / (3 * C ** 0.5)).bfloat16())
@@ -35,10 +35,10 @@ def test_conv3x3_matches_fp32(N, H, W, C, Co, bias):
     assert err <= 2e-2 * ref.abs().max().item() + 1e-3, err
 
 
-def test_conv3x3_autograd_backward_is_pytorchs():
+def test_conv3x3_autograd_backward_is_pytorchs(monkeypatch):
     from kubernetes_cloud_amd.ops import conv as kconv
     from kubernetes_cloud_amd.ops.conv import conv3x3
-    kconv._MODE = "all"
+    monkeypatch.setattr(kconv, "_MODE", "all")
     g = torch.Generator(device=dev).manual_seed(7)
     x = _cl(torch.randn(2, 64, 8, 8, device=dev, generator=g).bfloat16()).requires_grad_()
     w = _cl((torch.randn(128, 64, 3, 3, device=dev, generator=g) / 24).bfloat16()).requires_grad_()

@@ -100,7 +100,7 @@ def test_sample_greedy_and_masks(V):
             assert bool(keep[ids[b]]), (t, k, p, b)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_sample_topk_topp_distribution(dtype):
     """Top-k + top-p sampling draws from the renormalised kept set: fp32 logits take the memory-pass
     kernel (top-k survivors compacted in LDS), bf16 the register-resident one."""
@@ -265,17 +265,20 @@ def test_skinny_gemm_row_per_wave_kernel(M):
     assert (skinny_linear(x, w).float() - ref).abs().max() < 0.05
 
 
-@pytest.mark.parametrize("M,N,K", [(1, 12288, 4096), (2, 4096, 4096), (4, 4096, 4096), (1, 5376, 14336),
-                                   (2, 1024, 14336), (3, 4096, 4096)])
-@pytest.mark.parametrize("nres", [0, 1, 2])
-@pytest.mark.parametrize("split", [False, True])
+_LN_SKINNY_SHAPES = [(1, 12288, 4096), (2, 4096, 4096), (4, 4096, 4096), (1, 5376, 14336), (2, 1024, 14336),
+                     (3, 4096, 4096)]
+# every (split, nres, shape) except split with M != 1: the split path is M == 1 only
+_LN_SKINNY_CASES = [(M, N, K, nres, split) for split in (False, True) for nres in (0, 1, 2)
+                    for (M, N, K) in _LN_SKINNY_SHAPES if not (split and M != 1)]
+
+
+@pytest.mark.parametrize("M,N,K,nres,split", _LN_SKINNY_CASES,
+                         ids=[f"{c[4]}-{c[3]}-{c[0]}-{c[1]}-{c[2]}" for c in _LN_SKINNY_CASES])
 def test_ln_skinny_gemm(M, N, K, nres, split, monkeypatch):
     """split: at M = 1 the LN runs once (kca_ln_rows) before the plain GEMV;
     otherwise every GEMV workgroup normalises its activation slice itself."""
     from kubernetes_cloud_amd.ops import gemv
     monkeypatch.setattr(gemv, "_LN_SPLIT_M1", split)
-    if split and M != 1:
-        pytest.skip("the split path is M == 1 only")
     torch.manual_seed(M * 7 + N + K + nres)
     x = torch.randn(M, K, device=dev).to(torch.bfloat16)
     res = tuple(torch.randn(M, K, device=dev).to(torch.bfloat16) for _ in range(nres))

@@ -60,3 +60,36 @@ def test_decode_workspace_reserves_fanin_counters():
     assert n == cw + B * H * ns * (D + 2)
     assert cw % 4 == 0 and cw >= B * H  # 16-B aligned partials after the counters
     assert dops.decode_ws_floats(B, H, Hkv, D, 64, 64) == 0  # one split: no workspace
+
+
+def test_skinny_mm_workspace_pairs_are_never_freed(monkeypatch):
+    """ops/skinny_mm.py's split-K workspace contract: a (ws, bcnt) pair that a launch was handed may be
+    baked into a captured graph, so growing the workspace must keep the outgrown pair alive; growth is
+    geometric and a fitting request reuses the current pair."""
+    import gc
+    import types
+    import weakref
+
+    from kubernetes_cloud_amd.ops import skinny_mm as sm
+    monkeypatch.setattr(sm, "_WS", {})
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=0))
+    refs, sizes = [], []
+    need = 65536
+    for _ in range(4):
+        ws, bc = sm._workspace("cpu", need, 4096)
+        assert ws.dtype == torch.float32 and bc.dtype == torch.int32
+        assert ws.numel() >= need and bc.numel() >= 4096 and int(bc.abs().sum()) == 0
+        ws2, bc2 = sm._workspace("cpu", need // 2, 16)  # fits: the same pair
+        assert ws2.data_ptr() == ws.data_ptr() and bc2.data_ptr() == bc.data_ptr()
+        refs += [weakref.ref(ws), weakref.ref(bc)]
+        sizes.append(ws.numel())
+        need = ws.numel() + 1  # one float more than the pair holds: the next call must grow
+        del ws, bc, ws2, bc2
+    gc.collect()
+    assert all(r() is not None for r in refs)  # four distinct pairs, all alive
+    assert len({r().data_ptr() for r in refs}) == len(refs)
+    assert all(b >= 2 * a for a, b in zip(sizes, sizes[1:]))  # geometric: the kept list stays short
+    # another stream has its own pair (two streams never share arrival counters)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=7))
+    ws, bc = sm._workspace("cpu", 16, 16)
+    assert all(bc.data_ptr() != r().data_ptr() for r in refs)

@@ -222,3 +222,137 @@ def test_consumer_merged_row_stats(M, N, monkeypatch):
     ref = sm.mm_reference([(sm.ln_on_load_reference(outs[True][0], sm.row_stats_reference(outs[True][0], 1e-5),
                                                      gam, bet), wn, None)])
     _close(outs[True][1], ref, 1.5e-2)
+
+
+# ------------------------------------------------------------------ split-K workspace under graph capture
+_GN, _GK = 1024, 4096
+
+
+def _graph_operands(M, seed, w=None):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    x = torch.randn(M, _GK, generator=g, device=DEV).bfloat16()
+    if w is None:
+        w = _w(_GN, _GK, torch.bfloat16, g)
+    return x, w, torch.empty(M, _GN, device=DEV, dtype=torch.bfloat16)
+
+
+def _graph_launch(x, w, y, ks):
+    sm.launch([sm.job([sm.part(x, w)], _GN, y)], x.shape[0], torch.bfloat16, ks=ks)
+
+
+def _spy_workspace(monkeypatch):
+    """Empty workspace table; weak references to (and sizes of) every pair a launch is handed."""
+    import weakref
+    monkeypatch.setattr(sm, "_WS", {})
+    handed, real = [], sm._workspace
+
+    def spy(device, floats, nblk):
+        ws, bc = real(device, floats, nblk)
+        handed.append((weakref.ref(ws), weakref.ref(bc), ws.numel(), bc.numel()))
+        return ws, bc
+
+    monkeypatch.setattr(sm, "_workspace", spy)
+    return handed
+
+
+def _capture_small_then_large(monkeypatch):
+    """Graph A (M = 8, K split 4) and then graph B (M = 64, K split 32, a larger workspace) captured on
+    torch's capture stream into one pool, as the decode runner captures its (batch, kv-bucket) graphs.
+    B's capture also allocates tensors of the size of A's counters and partials, filled with non-zero /
+    NaN on replay: if A's pair went back to the pool when B outgrew it, these are the likeliest tensors
+    to land on it."""
+    import gc
+    handed = _spy_workspace(monkeypatch)
+    xA, w, yA = _graph_operands(8, 11)
+    xB, _, yB = _graph_operands(64, 12, w)
+    bf = torch.bfloat16
+    kA, fA, nA = sm.plan([sm.job([sm.part(xA, w)], _GN, yA)], 8, bf, ks=4)
+    kB, fB, nB = sm.plan([sm.job([sm.part(xB, w)], _GN, yB)], 64, bf, ks=32)
+    assert kA > 1 and kB > 1  # both launches use the workspace
+    pool = torch.cuda.graph_pool_handle()
+    gA, gB = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gA, pool=pool):
+        _graph_launch(xA, w, yA, 4)
+    assert len(handed) == 1
+    wsA, cntA = handed[0][2], handed[0][3]
+    assert wsA >= fA and cntA >= nA
+    assert fB > wsA  # B cannot reuse what A's launch allocated
+    with torch.cuda.graph(gB, pool=pool):
+        _graph_launch(xB, w, yB, 32)
+        keep = (torch.full((cntA,), 0x5A5A5A5, device=DEV, dtype=torch.int32),
+                torch.full((wsA,), float("nan"), device=DEV, dtype=torch.float32))
+    assert len(handed) == 2 and handed[1][2] >= fB and handed[1][3] >= nB
+    gc.collect()
+    alive = [r() is not None for h in handed for r in h[:2]]
+    return dict(gA=gA, gB=gB, xA=xA, xB=xB, w=w, yA=yA, yB=yB, alive=alive, keep=keep)
+
+
+def test_graph_workspace_pairs_outlive_growth(monkeypatch):
+    """Every (ws, bcnt) pair handed to a launch is still alive after a later capture outgrew it: graph A
+    holds the addresses of its pair for as long as it is replayed (independent of whether the caching
+    allocator happens to reuse the blocks)."""
+    s = _capture_small_then_large(monkeypatch)
+    assert all(s["alive"]), s["alive"]
+
+
+def test_graph_replay_after_workspace_growth(monkeypatch):
+    """Replay B, then A: A's arrival counters must still start at zero and its partials must be its own,
+    so its output equals the eager launch bit for bit (split-K sums in slice order) and the fp32
+    reference within the usual bound; the same for B."""
+    s = _capture_small_then_large(monkeypatch)
+    eA, eB = torch.empty_like(s["yA"]), torch.empty_like(s["yB"])
+    _graph_launch(s["xA"], s["w"], eA, 4)
+    _graph_launch(s["xB"], s["w"], eB, 32)
+    s["yA"].fill_(float("nan"))
+    s["yB"].fill_(float("nan"))
+    s["gB"].replay()
+    s["gA"].replay()
+    torch.cuda.synchronize()
+    assert int(s["keep"][0][0]) == 0x5A5A5A5 and bool(torch.isnan(s["keep"][1]).all())
+    assert torch.equal(s["yA"], eA)
+    _close(s["yA"], sm.mm_reference([(s["xA"], s["w"], None)]), 1.5e-2)
+    assert torch.equal(s["yB"], eB)
+    _close(s["yB"], sm.mm_reference([(s["xB"], s["w"], None)]), 1.5e-2)
+
+
+def test_second_graph_replays_without_the_first(monkeypatch):
+    """Graph A allocates the pair inside its capture (the zero fill of the counters is a memset node of
+    A alone); a second graph that fits in A's pair is captured and replayed on its own, A never runs.
+    Its counters must be zeroed by its own graph. Guards the fix: before it, the outcome depended on
+    what the pool's memory happened to hold, so this could pass by luck."""
+    handed = _spy_workspace(monkeypatch)
+    xA, w, yA = _graph_operands(8, 21)
+    xC, _, yC = _graph_operands(8, 22, w)
+    assert sm.plan([sm.job([sm.part(xC, w)], _GN, yC)], 8, torch.bfloat16, ks=8)[0] > 1
+    pool = torch.cuda.graph_pool_handle()
+    gA, gC = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gA, pool=pool):
+        _graph_launch(xA, w, yA, 4)
+    with torch.cuda.graph(gC, pool=pool):
+        _graph_launch(xC, w, yC, 8)
+    assert len(handed) == 2 and handed[0][0]() is handed[1][0]() and handed[0][1]() is handed[1][1]()
+    eC = torch.empty_like(yC)
+    _graph_launch(xC, w, eC, 8)
+    yC.fill_(float("nan"))
+    for _ in range(2):  # and a second replay: the counters were re-armed
+        gC.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(yC, eC)
+    _close(yC, sm.mm_reference([(xC, w, None)]), 1.5e-2)
+
+
+def test_capture_id_names_the_running_capture():
+    """The once-per-capture zeroing rests on ``_capture_id``: 0 outside a capture, one positive id for
+    every launch of a capture (the HIP runtime's, not the per-call fallback), another for the next."""
+    dev = torch.device(DEV, torch.cuda.current_device())
+    cur = lambda: sm._capture_id(dev, torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
+    sm._abi_ok()
+    assert cur() == 0
+    seen = []
+    for _ in range(2):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            seen.append((cur(), cur()))
+            torch.zeros(8, device=DEV)
+    assert all(a == b and a > 0 for a, b in seen) and seen[0][0] != seen[1][0]
+    assert cur() == 0
