@@ -15,7 +15,7 @@ class _CrossEntropyFn(torch.autograd.Function):
             logits = logits.contiguous()
         labels = labels.contiguous().to(torch.int64)
         loss = torch.empty(n, device=logits.device, dtype=torch.float32)
-        lse = torch.empty_like(loss)
+        lse = torch.empty(2, n, device=logits.device, dtype=torch.float32)  # row max, log(sum exp(x - max))
         _lib.call("kca_cross_entropy_fwd", logits.data_ptr(), logits.stride(0), labels.data_ptr(),
                   n, V, ignore_index, loss.data_ptr(), lse.data_ptr(), _lib.stream())
         ctx.save_for_backward(logits, labels, lse)
