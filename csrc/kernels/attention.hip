@@ -676,11 +676,10 @@ __global__ void __launch_bounds__(256, (D <= 160 ? 2 : 1)) attn_bwd_dq_kernel(At
   }
 }
 
-// ====================================================== backward, D >= 128
-// 32x32x16 variants for head_dim 128 / 256 (GPT-J, BLOOM shards): a wave owns
-// 32 keys (dK/dV kernel) or 32 queries (dQ kernel), halving LDS bytes per
-// MFMA versus the 16-wide kernels above (each operand fragment feeds a 32-wide
-// MFMA). Q/dO/K tiles are read both by rows (ds_read_b128) and transposed
+// ====================================================== backward dQ, D = 256
+// 32x32x16 variant for head_dim 256: a wave owns 32 queries, halving LDS bytes
+// per MFMA versus the 16-wide kernel above (each operand fragment feeds a
+// 32-wide MFMA). K/V tiles are read both by rows (ds_read_b128) and transposed
 // (ds_read_b64_tr_b16), so they use an XOR-swizzled image with unpadded rows:
 // 16-B chunk c of row r lives at chunk c ^ (((r&3)<<2) | ((r>>2)&3)), which is
 // conflict free for both access kinds (rows are 16-chunk multiples).
@@ -709,159 +708,6 @@ __device__ __forceinline__ bf16x8 tr_a32(const bf16_t* base, int s, int hh, int 
   const int col = db * 32 + 16 * ((lane >> 4) & 1) + 4 * (gi & 3);
   const int ch = col >> 3, in = col & 7;
   return cat44(tr_read(base + swz_off<D>(row, ch) + in), tr_read(base + swz_off<D>(row + 8, ch) + in));
-}
-
-template <int D, bool CAUSAL>
-__global__ void __launch_bounds__(256, 1) attn_bwd_dkdv32_kernel(AttnBwdParams p) {
-  constexpr int BK = 128, BQ = 32;
-  constexpr int TSZ = BQ * D;
-  constexpr int BUF = 2 * TSZ + 2 * BQ * 2;
-  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * BUF];
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l32 = lane & 31, hh = lane >> 5;
-  const int nkb = (p.Sk + BK - 1) / BK;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int kb = lid % nkb, bh = lid / nkb;
-  const int b = bh / p.Hkv, hk = bh % p.Hkv;
-  const int grp = p.H / p.Hkv;
-  const int off = p.Sk - p.Sq;
-  int kv_end = p.Sk;
-  KCA_DASSERT(!p.kv_len || (p.kv_len[b] >= 0 && p.kv_len[b] <= p.Sk));
-  if (p.kv_len) kv_end = min(kv_end, p.kv_len[b]);
-  const int kw = kb * BK + wave * 32;
-  const int key = kw + l32;
-  const float sl2 = p.scale * LOG2E;
-  const bool dfull = p.d_real == D;
-
-  const bf16_t* kp = p.k + b * p.k_sb + hk * p.k_sh;
-  const bf16_t* vp = p.v + b * p.v_sb + hk * p.v_sh;
-  bf16x8 kf[D / 16], vf[D / 16];
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const int d0 = 16 * s + 8 * hh;
-    const bool ok = key < p.Sk && d0 < p.d_real;
-    kf[s] = ok ? ld_bf16x8(kp + (long long)key * p.k_st + d0) : zero_bf16x8();
-    vf[s] = ok ? ld_bf16x8(vp + (long long)key * p.v_st + d0) : zero_bf16x8();
-  }
-  f32x16 dk[D / 32], dv[D / 32];
-#pragma unroll
-  for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
-
-  int q_lo = 0;
-  if (CAUSAL) q_lo = max(0, kb * BK - off) & ~(BQ - 1);
-  const int q_end = p.window > 0 ? min(p.Sq, kb * BK + BK - 1 - off + p.window) : p.Sq;
-  const int nqt = q_end > q_lo ? (q_end - q_lo + BQ - 1) / BQ : 0;
-  const int total = (kb * BK < kv_end) ? nqt * grp : 0;
-  const bool key_ok = key < kv_end && (!p.key_mask || km_bit(p.key_mask, p.km_words, b, key));
-
-  Stager<D, BQ, 256> sq, sd;
-  float lse_r = INFINITY, dl_r = 0.f;
-  auto load_tile = [&](int it) {
-    const int hq = hk * grp + it / nqt;
-    const int qt = q_lo + (it % nqt) * BQ;
-    const bool full = dfull && (qt + BQ <= p.Sq);
-    sq.load(p.q + b * p.q_sb + hq * p.q_sh, p.q_st, qt, p.Sq, p.d_real, full);
-    sd.load(p.dout + b * p.do_sb + hq * p.do_sh, p.do_st, qt, p.Sq, p.d_real, full);
-    if (threadIdx.x < BQ) {
-      const int q = qt + threadIdx.x;
-      const long long li = ((long long)b * p.H + hq) * p.Sq + q;
-      lse_r = q < p.Sq ? p.lse[li] : INFINITY;
-      dl_r = q < p.Sq ? p.delta[li] : 0.f;
-    }
-  };
-  auto store_tile = [&](int buf) {
-    bf16_t* base = smem + buf * BUF;
-    store_swz(sq, base);
-    store_swz(sd, base + TSZ);
-    float* f = reinterpret_cast<float*>(base + 2 * TSZ);
-    if (threadIdx.x < BQ) {
-      f[threadIdx.x] = lse_r;
-      f[BQ + threadIdx.x] = dl_r;
-    }
-  };
-  if (total > 0) {
-    load_tile(0);
-    store_tile(0);
-  }
-  __syncthreads();
-  for (int it = 0; it < total; ++it) {
-    const int hq = hk * grp + it / nqt;
-    const int qt = q_lo + (it % nqt) * BQ;
-    const bf16_t* Qs = smem + (it & 1) * BUF;
-    const bf16_t* Ds = Qs + TSZ;
-    const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * TSZ);
-    const float* dl_s = lse_s + BQ;
-    if (it + 1 < total) load_tile(it + 1);
-    const bool active = !CAUSAL || (kw <= qt + BQ - 1 + off);
-    if (active) {
-      f32x16 sacc, dpacc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dpacc[r] = 0.f; }
-#pragma unroll
-      for (int s = 0; s < D / 16; ++s) {
-        const int o = swz_off<D>(l32, 2 * s + hh);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_bf16x8(Qs + o), kf[s], sacc, 0, 0, 0);
-        dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_bf16x8(Ds + o), vf[s], dpacc, 0, 0, 0);
-      }
-      const bool need_mask = (CAUSAL && (kw + 31 > qt + off)) || (kw + 32 > kv_end) || (qt + BQ > p.Sq) ||
-                             p.window > 0 || p.key_mask;
-      const float slope = p.alibi ? p.alibi[hq] * LOG2E : 0.f;
-      float pv[16], dsv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ql = (r & 3) + 8 * (r >> 2) + 4 * hh;
-        const int q = qt + ql;
-        float x = sacc[r] * sl2 - lse_s[ql] * LOG2E;
-        if (p.alibi) x += slope * (float)(key - q - off);
-        float pr = exp2f(x);
-        if (need_mask) {
-          bool valid = q < p.Sq && key_ok;
-          if (CAUSAL) valid = valid && (key <= q + off);
-          if (p.window > 0) valid = valid && (key > q + off - p.window);
-          pr = valid ? pr : 0.f;
-        }
-        pv[r] = pr;
-        dsv[r] = pr * (dpacc[r] - dl_s[ql]);
-      }
-      const bf16x8 pb0 = to_bf16x8(pv), pb1 = to_bf16x8(pv + 8);
-      const bf16x8 db0 = to_bf16x8(dsv), db1 = to_bf16x8(dsv + 8);
-#pragma unroll
-      for (int db = 0; db < D / 32; ++db) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_a32<D>(Ds, s, hh, lane, db), s ? pb1 : pb0,
-                                                           dv[db], 0, 0, 0);
-          dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_a32<D>(Qs, s, hh, lane, db), s ? db1 : db0,
-                                                           dk[db], 0, 0, 0);
-        }
-      }
-    }
-    if (it + 1 < total) store_tile((it + 1) & 1);
-    __syncthreads();
-  }
-  if (key < p.Sk) {
-    bf16_t* dkp = p.dk + b * p.dk_sb + hk * p.dk_sh + (long long)key * p.dk_st;
-    bf16_t* dvp = p.dv + b * p.dv_sb + hk * p.dv_sh + (long long)key * p.dv_st;
-#pragma unroll
-    for (int db = 0; db < D / 32; ++db) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = db * 32 + 8 * g + 4 * hh;
-        if (d < p.d_real) {
-          uint2 w;
-          w.x = pack_bf16x2(dk[db][4 * g] * p.scale, dk[db][4 * g + 1] * p.scale);
-          w.y = pack_bf16x2(dk[db][4 * g + 2] * p.scale, dk[db][4 * g + 3] * p.scale);
-          *reinterpret_cast<uint2*>(dkp + d) = w;
-          w.x = pack_bf16x2(dv[db][4 * g], dv[db][4 * g + 1]);
-          w.y = pack_bf16x2(dv[db][4 * g + 2], dv[db][4 * g + 3]);
-          *reinterpret_cast<uint2*>(dvp + d) = w;
-        }
-      }
-    }
-  }
 }
 
 template <int D, bool CAUSAL>
@@ -1123,27 +969,16 @@ KCA_API int kca_attn_bwd(const void* q, const void* k, const void* v,
                   dv_sb, dv_st, dv_sh,
                   B, Sq, Sk, H, Hkv, d_real, causal, scale, alibi, kv_len, window, key_mask, (Sk + 31) / 32};
   if (D == 256) {  // dQ on the 32-wide kernel (D=128 measured faster on the 16-wide pair: occupancy)
-    dim3 h1(((Sk + 127) / 128) * B * Hkv);
+    // K, V, dK^T, dV^T of 32 keys exceed the 512-register file, so the dK/dV pass keeps 16 keys
+    // per wave.
     dim3 h2(((Sq + 127) / 128) * B * H);
     dim3 g1w(((Sk + 63) / 64) * B * Hkv);
-    if (D == 128) {
-      if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<128, true>), h1, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL((attn_bwd_dq32_kernel<128, true>), h2, dim3(256), 0, stream, p);
-      } else {
-        hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<128, false>), h1, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL((attn_bwd_dq32_kernel<128, false>), h2, dim3(256), 0, stream, p);
-      }
+    if (causal) {
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<256, true>), g1w, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_bwd_dq32_kernel<256, true>), h2, dim3(256), 0, stream, p);
     } else {
-      // D = 256: K, V, dK^T, dV^T of 32 keys exceed the 512-register file, so
-      // the dK/dV pass keeps 16 keys per wave; dQ uses the 32-wide kernel.
-      if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<256, true>), g1w, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL((attn_bwd_dq32_kernel<256, true>), h2, dim3(256), 0, stream, p);
-      } else {
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<256, false>), g1w, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL((attn_bwd_dq32_kernel<256, false>), h2, dim3(256), 0, stream, p);
-      }
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<256, false>), g1w, dim3(256), 0, stream, p);
+      hipLaunchKernelGGL((attn_bwd_dq32_kernel<256, false>), h2, dim3(256), 0, stream, p);
     }
     return 0;
   }

@@ -111,13 +111,15 @@ def _masks(kv_len):
 
 
 def _fwd(q, k, v, causal, scale, kv_len, alibi, out=None, window: int = 0, rowsum_col: int = -1,
-         max_col: int = -1):
+         max_col: int = -1, lse=None, flags=None):
     B, Sq, H, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     o = out if out is not None else torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
-    lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
+    if lse is None:  # a caller's own contiguous [B, H, Sq] fp32 buffer (tests: between guard bands)
+        lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     # overflow flags of the full-tile fast path (4 per 128-row block)
-    flags = torch.empty(4 * ((Sq + 127) // 128) * B * H, device=q.device, dtype=torch.int32)
+    if flags is None:  # a caller's own int32 buffer of that size (tests read the flags back)
+        flags = torch.empty(4 * ((Sq + 127) // 128) * B * H, device=q.device, dtype=torch.int32)
     lens, km = _masks(kv_len)
     _lib.call("kca_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
               *_strides(q), *_strides(k), *_strides(v), *_strides(o),

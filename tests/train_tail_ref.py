@@ -89,7 +89,7 @@ def ulp_bound(x: torch.Tensor, n_ulps: float, fmt: str = "fp32") -> torch.Tensor
     return n_ulps * (ulp32(x) if fmt == "fp32" else ulp_bf16(x))
 
 
-def assert_within(name: str, actual: torch.Tensor, expected64: torch.Tensor, bound64) -> float:
+def assert_within(name: str, actual: torch.Tensor, expected64: torch.Tensor, bound64, prefix: str = "train-tail") -> float:
     """Per element |actual - expected| <= bound. Non-finite expected values must be reproduced (NaN as
     NaN, an infinity with its sign). Prints and records the worst error/bound ratio; on failure
     reports the worst index with its values."""
@@ -105,7 +105,7 @@ def assert_within(name: str, actual: torch.Tensor, expected64: torch.Tensor, bou
     ratio = torch.where(err == 0, torch.zeros_like(err), err / b)  # bound 0 and error > 0 -> inf
     worst = float(ratio.max()) if ratio.numel() else 0.0
     WORST[name] = max(WORST.get(name, 0.0), worst)
-    print(f"[train-tail] {name}: worst error/bound {worst:.3g} over {ratio.numel()} elements")
+    print(f"[{prefix}] {name}: worst error/bound {worst:.3g} over {ratio.numel()} elements")
     if not worst <= 1.0:
         i = int(ratio.argmax())
         raise AssertionError(f"{name}: element {i}: got {a[i].item()!r}, expected {e[i].item()!r}, "
