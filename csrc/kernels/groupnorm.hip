@@ -243,9 +243,15 @@ __global__ void __launch_bounds__(256) gn_slice_stats(const bf16_t* __restrict__
   const long long grp = blockIdx.x / S;
   const long long a = (long long)(blockIdx.x % S) * SL, e = min(a + SL, Lg);
   const bf16_t* p = x + grp * Lg;
-  const float K = bf2f(p[a]);
+  // The shift is each thread's own first element, not the slice's: with one K for the slice a
+  // single outlier there (|K - mean| >> std) put the cancellation of s2 - s1^2 / cnt into all 256
+  // partials at once (rstd off by 2.6e-5 relative on a 10264-element slice that starts with an 8
+  // among values of 0.016); now it costs the one thread that starts on it.
+  const bool vec = (SL % 8) == 0 && (Lg % 8) == 0;
+  const long long first = vec ? (a / 8 + threadIdx.x) * 8 : a + threadIdx.x;
+  const float K = first < e ? bf2f(p[first]) : 0.f;
   float cnt = 0.f, s1 = 0.f, s2 = 0.f;
-  if ((SL % 8) == 0 && (Lg % 8) == 0) {
+  if (vec) {
     for (long long i = a / 8 + threadIdx.x; i < e / 8; i += blockDim.x) {
       float v[8];
       load8(p + i * 8, v);
@@ -443,7 +449,7 @@ __global__ void __launch_bounds__(256) gn_dx_v(const bf16_t* __restrict__ dy, co
 KCA_API int kca_groupnorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
                               float* part, int N, int C, int hw, int G, float eps, int silu,
                               hipStream_t stream) {
-  if (C % G) return 1;
+  if (G <= 0 || N <= 0 || hw <= 0 || C <= 0 || C % G) return 1;  // before any division by G or N * G
   const int cpg = C / G;
   const long long NG = (long long)N * G, Lg = (long long)cpg * hw;
   long long S = (2048 + NG - 1) / NG;           // ~2048 workgroups
@@ -465,7 +471,7 @@ KCA_API int kca_groupnorm_fwd(const void* x, const void* w, const void* b, void*
 KCA_API int kca_groupnorm_bwd(const void* dy, const void* x, const void* w, const void* b, const float* mean,
                               const float* rstd, void* dx, void* dw, void* db, float* ws, int N, int C,
                               int hw, int G, int silu, hipStream_t stream) {
-  if (C % G) return 1;
+  if (G <= 0 || N <= 0 || hw <= 0 || C <= 0 || C % G) return 1;
   const int planes = N * C;
   if (hw % 8 == 0) {
     if (hw >= 2048) {

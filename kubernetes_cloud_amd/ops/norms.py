@@ -3,6 +3,12 @@
 GPU tensors run ``csrc/kernels/layernorm.hip`` / ``groupnorm.hip``; CPU tensors
 run the fp32 PyTorch reference below (the numerics the kernel tests compare
 against).
+
+The kernels read gamma/beta as bf16. ``weight``/``bias`` of another dtype (norms kept in fp32, an
+fp32 module fed bf16 activations) are handed to them as bf16 copies, so the native path consumes
+gamma/beta rounded to bf16; their gradients come back in the parameter's own dtype (LayerNorm:
+summed and written in fp32 by the kernel, no bf16 round trip; GroupNorm: the kernel's bf16
+dw/db cast).
 """
 from __future__ import annotations
 
@@ -10,6 +16,13 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+
+
+def _bf16(t: torch.Tensor | None) -> torch.Tensor | None:
+    """The bf16 tensor the kernels read for a parameter (itself when it already is one)."""
+    if t is None or t.dtype == torch.bfloat16:
+        return t
+    return t.to(torch.bfloat16)
 
 
 def _ln_ref(h: torch.Tensor, w, b, eps):
@@ -32,10 +45,13 @@ class _LayerNormFn(torch.autograd.Function):
         # inside the argument list is recycled by the next allocation (r2's copy)
         r1c = r1.contiguous() if r1 is not None else None
         r2c = r2.contiguous() if r2 is not None else None
+        wk, bk = _bf16(weight), _bf16(bias)
         _lib.call("kca_layernorm_fwd", x2.data_ptr(), _lib.ptr(r1c), _lib.ptr(r2c), _lib.ptr(h),
-                  weight.data_ptr(), _lib.ptr(bias), y.data_ptr(), mean.data_ptr(),
+                  wk.data_ptr(), _lib.ptr(bk), y.data_ptr(), mean.data_ptr(),
                   rstd.data_ptr(), rows, d, float(eps), _lib.stream())
-        ctx.save_for_backward(h if has_res else x2, weight, mean, rstd)
+        ctx.save_for_backward(h if has_res else x2, wk, mean, rstd)
+        ctx.wdtype = weight.dtype
+        ctx.bdtype = bias.dtype if bias is not None else None
         ctx.has_bias = bias is not None
         ctx.has_res = has_res
         ctx.n_res = (r1 is not None) + (r2 is not None)
@@ -52,16 +68,19 @@ class _LayerNormFn(torch.autograd.Function):
         dx = torch.empty_like(h)
         parts = _lib.require().kca_layernorm_bwd_parts(rows)
         ws = torch.empty(2 * parts * d, device=h.device, dtype=torch.float32)
-        dw = torch.empty_like(weight)
-        db = torch.empty_like(weight) if ctx.has_bias else None
+        # bf16 parameters: bf16 sums; any other dtype: the kernel's fp32 sums, cast once if need be
+        pf32 = ctx.wdtype != torch.bfloat16 or (ctx.has_bias and ctx.bdtype != torch.bfloat16)
+        pdt = torch.float32 if pf32 else torch.bfloat16
+        dw = torch.empty(d, device=h.device, dtype=pdt)
+        db = torch.empty(d, device=h.device, dtype=pdt) if ctx.has_bias else None
         dres = dh.contiguous() if (ctx.has_res and dh is not None) else None
         _lib.call("kca_layernorm_bwd", dy.data_ptr(), h.data_ptr(), mean.data_ptr(),
                   rstd.data_ptr(), weight.data_ptr(), _lib.ptr(dres), dx.data_ptr(),
-                  dw.data_ptr(), _lib.ptr(db), int(weight.dtype == torch.float32),
+                  dw.data_ptr(), _lib.ptr(db), int(pf32),
                   ws.data_ptr(), rows, d, _lib.stream())
         g1 = dx if ctx.n_res >= 1 else None
         g2 = dx if ctx.n_res >= 2 else None
-        return dx, dw, db, None, g1, g2
+        return dx, dw.to(ctx.wdtype), (db.to(ctx.bdtype) if db is not None else None), None, g1, g2
 
 
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None,
@@ -97,6 +116,8 @@ class _GroupNormFn(torch.autograd.Function):
         mean = torch.empty(n * groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         part = torch.empty(2 * n * c, device=x.device, dtype=torch.float32)
+        ctx.wdtype, ctx.bdtype = weight.dtype, (bias.dtype if bias is not None else None)
+        weight, bias = _bf16(weight), _bf16(bias)
         _lib.call("kca_groupnorm_fwd", x.data_ptr(), weight.data_ptr(), _lib.ptr(bias),
                   y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), part.data_ptr(), n, c, hw, groups,
                   float(eps), int(silu), _lib.stream())
@@ -118,7 +139,7 @@ class _GroupNormFn(torch.autograd.Function):
                   _lib.ptr(bias), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
                   dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, c, hw, ctx.groups,
                   int(ctx.silu), _lib.stream())
-        return dx, dw, (db if bias is not None else None), None, None, None
+        return dx, dw.to(ctx.wdtype), (db.to(ctx.bdtype) if bias is not None else None), None, None, None
 
 
 class _GroupNormNHWCFn(torch.autograd.Function):
@@ -132,6 +153,8 @@ class _GroupNormNHWCFn(torch.autograd.Function):
         mean = torch.empty(n * groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         ws = torch.empty(_lib.require().kca_groupnorm_nhwc_ws(n, p, c), device=x.device, dtype=torch.float32)
+        ctx.wdtype, ctx.bdtype = weight.dtype, (bias.dtype if bias is not None else None)
+        weight, bias = _bf16(weight), _bf16(bias)
         _lib.call("kca_groupnorm_nhwc_fwd", x.data_ptr(), weight.data_ptr(), _lib.ptr(bias), y.data_ptr(),
                   mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), n, p, c, groups, float(eps), int(silu),
                   _lib.stream())
@@ -153,7 +176,7 @@ class _GroupNormNHWCFn(torch.autograd.Function):
         _lib.call("kca_groupnorm_nhwc_bwd", dy.data_ptr(), x.data_ptr(), weight.data_ptr(), _lib.ptr(bias),
                   mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dw.data_ptr(), _lib.ptr(db), ws.data_ptr(),
                   n, p, c, ctx.groups, int(ctx.silu), _lib.stream())
-        return dx, dw, db, None, None, None
+        return dx, dw.to(ctx.wdtype), (db.to(ctx.bdtype) if db is not None else None), None, None, None
 
 
 def _channels_last(x: torch.Tensor) -> bool:
@@ -165,6 +188,7 @@ def _group_norm_nhwc_add(x, add, weight, bias, groups, eps, silu):
     n, c = x.shape[0], x.shape[1]
     p = x.numel() // (n * c)
     add = add.to(torch.float32)
+    weight, bias = _bf16(weight), _bf16(bias)
     if add.stride(1) != 1 or add.stride(0) < c:  # a row-strided slice (the UNet's batched time GEMM) is read in place
         add = add.contiguous()
     y = torch.empty_like(x)
@@ -211,6 +235,7 @@ def group_norm_cat(x1: torch.Tensor, x2: torch.Tensor, groups: int, weight: torc
         cat = torch.cat([d1, x2], dim=1)
         return group_norm(cat, groups, weight, bias, eps, silu=silu), (cat if want_raw else None)
     C, P = C1 + C2, H * W
+    weight, bias = _bf16(weight), _bf16(bias)
     y = torch.empty(N, H, W, C, device=x2.device, dtype=x2.dtype).permute(0, 3, 1, 2)
     raw = torch.empty(N, H, W, C, device=x2.device, dtype=x2.dtype).permute(0, 3, 1, 2) if want_raw else None
     add = None
