@@ -940,8 +940,20 @@ KCA_API int kca_attn_bwd_tiled(const void* q, const void* k, const void* v, cons
                                long long dk_st, long long dk_sh, long long dv_sb, long long dv_st,
                                long long dv_sh, int B, int Sq, int Sk, int H, int Hkv, int d,
                                int causal, float scale, hipStream_t stream);
+KCA_API int kca_attn_bwd_tiled_ws(const void* q, const void* k, const void* v, const void* dout,
+                                  void* dq, void* dk, void* dv, const float* lse, const float* delta,
+                                  long long q_sb, long long q_st, long long q_sh, long long k_sb,
+                                  long long k_st, long long k_sh, long long v_sb, long long v_st,
+                                  long long v_sh, long long do_sb, long long do_st, long long do_sh,
+                                  long long dq_sb, long long dq_st, long long dq_sh, long long dk_sb,
+                                  long long dk_st, long long dk_sh, long long dv_sb, long long dv_st,
+                                  long long dv_sh, int B, int Sq, int Sk, int H, int Hkv, int d,
+                                  int causal, float scale, void* ws, long long ws_bytes, hipStream_t stream);
 
-KCA_API int kca_attn_bwd(const void* q, const void* k, const void* v,
+// kca_attn_bwd plus a dS workspace (kca_attn_bwd_ws_bytes): the full-tile path may hand dS from the
+// dK/dV kernel to the dQ kernel through it (attention_tiled.hip, bit 2 of the variant); with a null or
+// short workspace, another variant or an ineligible shape it is exactly kca_attn_bwd.
+KCA_API int kca_attn_bwd_ws(const void* q, const void* k, const void* v,
                          const void* o, const void* dout, void* dq, void* dk,
                          void* dv, const float* lse, const float* delta,
                          long long q_sb, long long q_st, long long q_sh,
@@ -953,13 +965,14 @@ KCA_API int kca_attn_bwd(const void* q, const void* k, const void* v,
                          long long dv_sb, long long dv_st, long long dv_sh,
                          int B, int Sq, int Sk, int H, int Hkv, int d_real,
                          int causal, float scale, const float* alibi,
-                         const int* kv_len, int window, const unsigned* key_mask, hipStream_t stream) {
+                         const int* kv_len, int window, const unsigned* key_mask, void* ws,
+                         long long ws_bytes, hipStream_t stream) {
   if (d_real % 8 || H % Hkv || window < 0) return 1;
   if (g_attn_tiled && !alibi && !kv_len && !window && !key_mask &&
-      kca_attn_bwd_tiled(q, k, v, dout, dq, dk, dv, lse, delta, q_sb, q_st, q_sh, k_sb, k_st, k_sh,
-                         v_sb, v_st, v_sh, do_sb, do_st, do_sh, dq_sb, dq_st, dq_sh, dk_sb, dk_st,
-                         dk_sh, dv_sb, dv_st, dv_sh, B, Sq, Sk, H, Hkv, d_real, causal, scale,
-                         stream) == 0)
+      kca_attn_bwd_tiled_ws(q, k, v, dout, dq, dk, dv, lse, delta, q_sb, q_st, q_sh, k_sb, k_st, k_sh,
+                            v_sb, v_st, v_sh, do_sb, do_st, do_sh, dq_sb, dq_st, dq_sh, dk_sb, dk_st,
+                            dk_sh, dv_sb, dv_st, dv_sh, B, Sq, Sk, H, Hkv, d_real, causal, scale, ws,
+                            ws_bytes, stream) == 0)
     return 0;
   const int D = pick_d(d_real);
   AttnBwdParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o,
@@ -994,4 +1007,23 @@ KCA_API int kca_attn_bwd(const void* q, const void* k, const void* v,
     }
   });
   return 0;
+}
+
+KCA_API int kca_attn_bwd(const void* q, const void* k, const void* v,
+                         const void* o, const void* dout, void* dq, void* dk,
+                         void* dv, const float* lse, const float* delta,
+                         long long q_sb, long long q_st, long long q_sh,
+                         long long k_sb, long long k_st, long long k_sh,
+                         long long v_sb, long long v_st, long long v_sh,
+                         long long do_sb, long long do_st, long long do_sh,
+                         long long dq_sb, long long dq_st, long long dq_sh,
+                         long long dk_sb, long long dk_st, long long dk_sh,
+                         long long dv_sb, long long dv_st, long long dv_sh,
+                         int B, int Sq, int Sk, int H, int Hkv, int d_real,
+                         int causal, float scale, const float* alibi,
+                         const int* kv_len, int window, const unsigned* key_mask, hipStream_t stream) {
+  return kca_attn_bwd_ws(q, k, v, o, dout, dq, dk, dv, lse, delta, q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st,
+                         v_sh, do_sb, do_st, do_sh, dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb, dv_st, dv_sh,
+                         B, Sq, Sk, H, Hkv, d_real, causal, scale, alibi, kv_len, window, key_mask, nullptr, 0,
+                         stream);
 }

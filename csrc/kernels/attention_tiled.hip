@@ -871,6 +871,11 @@ struct FastBwdParams {
   int B, Sq, Sk, H, Hkv;
   float scale;
 };
+// + the dS tiles handed from attn_bwd_dkdv_w8_kernel<.., EMIT_DS> to attn_bwd_dq_ds_kernel (a type of its
+// own: the kernels without a workspace keep their argument block)
+struct FastBwdWsParams : FastBwdParams {
+  bf16_t* ws;
+};
 
 // A operand (32 rows x 16 k) read by rows from an image: lane (row l32, half hh)
 // takes chunk 2s+hh of its row. Returns the two per-lane bases (s even / odd).
@@ -1064,6 +1069,155 @@ __global__ void __launch_bounds__(256, (D <= 64 && !CAUSAL) ? 4 : 1) attn_bwd_dq
                         smem + wave * 32 * D * 2);
   ASTAMP(6);
   ASTAMP_FLUSH(16);
+}
+
+// dQ from the dS that attn_bwd_dkdv_w8_kernel<.., EMIT_DS> left in p.ws (bit 2 of g_attn_variant; D = 256,
+// H == Hkv): dQ = dS.K, a causal-triangular GEMM with no S / dP MFMAs, no exp2 and no Q, dO, V, lse or
+// delta traffic. Grid, block order, tile bounds, K staging and the K^T A operand are the kernel's above.
+// Workspace layout (private to the two kernels): ws[b][h][q / 32][key / 32] is a 2 KB tile
+// [frag 2][lane 64][8 bf16], the producer's registers: chunk (frag, 32 hh + key) holds the query quads
+// qq = hh + 4 frag and qq + 2 (queries 4 qq .. + 3) of its key. A wave loads its tile with two 16-byte
+// loads per lane, one step ahead, and writes the quads into a wave-private LDS tile dS^T[key 32][q 32],
+// byte 64 key + 8 (qq ^ (key >> 2)) (the XOR spreads the 8-byte writes over all banks and keeps the
+// reads conflict-free). Four transposing reads then give lane (q l32, half hh) the keys (r&3) +
+// 8(r>>2) + 4hh (+ 16 for the second fragment) in k-slots 8hh + r, the slots the kernel above fills
+// from its own S^T accumulator, so every dQ MFMA sums the same products in the same order and dQ has
+// the same bits. The masked tiles arrive as zeros.
+// Two workgroups per CU: 128 accumulators and no Q / dO fragments leave room for two waves per SIMD.
+template <int D, bool CAUSAL>
+__global__ void __launch_bounds__(256, 2) attn_bwd_dq_ds_kernel(FastBwdWsParams p) {
+  constexpr int BM = 128, BN = 32;
+  constexpr int TILE = BN * D * 2;
+  constexpr int NCH = D / 8, CPT = 32 * NCH / 256, RPI = 256 / NCH;
+  constexpr int DST = BN * 32 * 2;   // one dS tile
+  constexpr int DOFF = 2 * TILE;     // dS tiles: [buf 2][wave 4]
+  __shared__ __attribute__((aligned(16))) char smem[4 * TILE];  // the epilogue takes 4 images
+  static_assert(DOFF + 2 * 4 * DST <= 4 * TILE && 256 % NCH == 0, "dQ from dS: LDS plan");
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hh = lane >> 5;
+  const int nqb = p.Sq / BM;
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int qi = lid % nqb;
+  const int qb = CAUSAL ? (nqb - 1 - qi) : qi;
+  const int bh = lid / nqb;
+  const int b = bh / p.H, h = bh % p.H;
+  const int off = p.Sk - p.Sq;
+  const int q0 = qb * BM + wave * 32;
+  int kv_hi = p.Sk;
+  if (CAUSAL) kv_hi = min(kv_hi, qb * BM + BM + off);
+  const int ntiles = (kv_hi + BN - 1) / BN;
+
+  f32x16 dq[D / 32];
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
+
+  // K rows as in Stager (thread tid: chunk tid % NCH of rows tid / NCH + i * RPI), K only
+  const __amdgpu_buffer_rsrc_t rk = head_rsrc(p.k + b * p.k_sb + h * p.k_sh);
+  int vok[CPT], lk[CPT];
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    vok[i] = (int)(((long long)(tid / NCH + i * RPI) * p.k_st + (tid % NCH) * 8) * 2);
+    lk[i] = img_off<D>(tid / NCH + i * RPI, tid % NCH);
+  }
+  // this wave's row of dS tiles
+  const __amdgpu_buffer_rsrc_t rw = head_rsrc(p.ws + (long long)bh * p.Sq * p.Sk);
+  const int ws_row = __builtin_amdgcn_readfirstlane((q0 / 32) * (p.Sk / 32) * DST);
+  const int wv = lane * 16;
+  char* const dsl = smem + DOFF + wave * DST;
+  // LDS write: this lane's chunk is key l32, quads hh + 2m (m = 0, 1: load 0; 2, 3: load 1)
+  // transposing read n (keys 8n ..): 16 lanes take keys 4hh .. + 3 of q columns 16 grp .. + 15, each its quad
+  int dsw[4], dsr[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int l32 = lane & 31, key = 8 * n + 4 * hh + ((lane & 15) >> 2), qq = 4 * ((lane >> 4) & 1) + (lane & 3);
+    dsw[n] = 64 * l32 + 8 * ((hh + 2 * n) ^ (l32 >> 2));
+    dsr[n] = 64 * key + 8 * (qq ^ (key >> 2));
+  }
+  int b1, b2;
+  tr_bases<D>(lane, b1, b2);
+
+  // K comes from L2 one step ahead; the dS stream comes from HBM and is read once, so it runs PD tiles
+  // ahead in a ring of PD register sets (tile t in set t % PD; ntiles is a multiple of 4, Sq and Sk being multiples of 128): with one step
+  // of prefetch the loop waited out the HBM latency every step (456 us at the bench shape).
+  constexpr int PD = 2;
+  u32x4 sk[CPT], sd[PD][2];
+  auto load_k = [&](int t) {
+    const int sok = __builtin_amdgcn_readfirstlane((int)(t * BN * p.k_st * 2));
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rk, vok[i], sok, 0);
+      sk[i] = *reinterpret_cast<const u32x4*>(&a);
+    }
+  };
+  auto load_ds = [&](int t, auto set) {
+    const int so = __builtin_amdgcn_readfirstlane(ws_row + t * DST);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {  // read once: non-temporal
+      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rw, wv, so + i * (DST / 2), 2);
+      sd[decltype(set)::value][i] = *reinterpret_cast<const u32x4*>(&a);
+    }
+  };
+  auto store_tile = [&](int buf, auto set) {
+    constexpr int J = decltype(set)::value;
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) *reinterpret_cast<u32x4*>(smem + buf * TILE + lk[i]) = sk[i];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      *reinterpret_cast<u32x2*>(dsl + buf * 4 * DST + dsw[2 * i]) = u32x2{sd[J][i][0], sd[J][i][1]};
+      *reinterpret_cast<u32x2*>(dsl + buf * 4 * DST + dsw[2 * i + 1]) = u32x2{sd[J][i][2], sd[J][i][3]};
+    }
+  };
+  const int last = ntiles - 1;
+
+  load_k(0);
+  load_ds(0, std::integral_constant<int, 0>{});
+  store_tile(0, std::integral_constant<int, 0>{});
+  // issue order as in the loop (dS tile 1 .. PD - 1, K tile 1, dS tile PD): the loop's waits are counted for it
+  static_for<1, PD>([&](auto T) { load_ds(min(decltype(T)::value, last), T); });
+  __builtin_amdgcn_sched_barrier(0);
+  load_k(min(1, last));
+  __builtin_amdgcn_sched_barrier(0);
+  load_ds(min(PD, last), std::integral_constant<int, 0>{});
+  __syncthreads();
+  // step t: tile t from LDS; then tile t + 1 (K registers, dS set (t + 1) % PD) into the other buffers
+  // and the loads of K tile t + 2 and dS tile t + 1 + PD, the K load first: its wait then leaves the
+  // younger dS loads in flight
+  auto tile_step = [&](int t, auto jc) {
+    constexpr int NX = (decltype(jc)::value + 1) % PD;
+    const char* Ks = smem + (t & 1) * TILE;
+    const char* ds = dsl + (t & 1) * 4 * DST;
+    const bf16x8 d0 = cat8(lds_tr4(ds, dsr[0]), lds_tr4(ds, dsr[1]));
+    const bf16x8 d1 = cat8(lds_tr4(ds, dsr[2]), lds_tr4(ds, dsr[3]));
+    {
+      bf16x8 t0[2], t1[2];
+      t0[0] = tr_frag<D>(Ks, b1, b2, 0, 0);
+      t1[0] = tr_frag<D>(Ks, b1, b2, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+      for (int db = 0; db < D / 32; ++db) {
+        if (db + 1 < D / 32) {
+          t0[(db + 1) & 1] = tr_frag<D>(Ks, b1, b2, 0, db + 1);
+          t1[(db + 1) & 1] = tr_frag<D>(Ks, b1, b2, 1, db + 1);
+          __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+        }
+        dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t0[db & 1], d0, dq[db], 0, 0, 0);
+        dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1[db & 1], d1, dq[db], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+      }
+    }
+    asm volatile("" ::: "memory");
+    if (t + 1 < ntiles) store_tile((t + 1) & 1, std::integral_constant<int, NX>{});
+    load_k(min(t + 2, last));
+    load_ds(min(t + 1 + PD, last), std::integral_constant<int, NX>{});
+    __syncthreads();
+  };
+  for (int t = 0; t < ntiles; t += PD)
+    static_for<0, PD>([&](auto J) { tile_step(t + decltype(J)::value, J); });
+  store_tile_lds<D>(p.dq + b * p.dq_sb + h * p.dq_sh + (long long)q0 * p.dq_st, p.dq_st, dq, lane, p.scale,
+                    smem + wave * 32 * D * 2);
 }
 
 // 64-wide heads without a causal mask (SD-1.5's 40-wide heads in narrow storage): registers capped for
@@ -1294,8 +1448,40 @@ __global__ void __launch_bounds__(256, (D <= 64 && !CAUSAL) ? 3 : 1) attn_bwd_dk
 // the 4-wave kernel's: dK and dV come out bit-identical to it.
 // LDS per tile step and pair: Q rows 16 KB + dO^T 16 KB + P 4 KB written (V wave), dO rows 16 KB +
 // Q^T 16 KB + P 4 KB read (K wave) = 72 KB; per workgroup 288 KB + the 32 KB staging store.
-template <int D, bool CAUSAL>
-__global__ void __launch_bounds__(512, 1) attn_bwd_dkdv_w8_kernel(FastBwdParams p) {
+// The K wave's dS stores of attn_bwd_dkdv_w8_kernel<.., EMIT_DS>; empty without the flag, so that
+// instantiation keeps its code.
+template <bool ON>
+struct DsEmitter {
+  __device__ __forceinline__ void init(const FastBwdParams&, int, int, int, int) {}
+  __device__ __forceinline__ void store(const bf16x8&, const bf16x8&, int) const {}
+};
+template <>
+struct DsEmitter<true> {
+  __amdgpu_buffer_rsrc_t r_;
+  int v_, dt_, t0_;
+  __device__ __forceinline__ void init(const FastBwdWsParams& p, int bh, int lane, int q_lo, int kw) {
+    r_ = head_rsrc(p.ws + (long long)bh * p.Sq * p.Sk);
+    v_ = lane * 16;
+    dt_ = (p.Sk / 32) * 2048;
+    t0_ = (q_lo / 32) * dt_ + (kw / 32) * 2048;
+  }
+  __device__ __forceinline__ void store(const bf16x8& s0, const bf16x8& s1, int t) const {
+    const int so = __builtin_amdgcn_readfirstlane(t0_ + t * dt_);
+    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&s0), r_, v_, so, 2);  // 2: non-temporal
+    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&s1), r_, v_, so + 1024, 2);
+  }
+};
+
+// EMIT_DS (bit 2 of g_attn_variant): the K wave also writes the bf16 dS of every tile step -- the
+// masked-to-zero tiles included -- to p.ws for attn_bwd_dq_ds_kernel, which then needs no S / dP / exp2
+// of its own. Workspace layout (private to the two kernels): ws[b][h][q / 32][key / 32] is a 2 KB tile
+// [frag 2][lane 64][8 bf16]: the K wave's s0 / s1 registers as they are, lane = 32 hh + key, element r
+// = query (r&3) + 8(r>>2) + 4hh + 16 frag. Two 16-byte non-temporal stores per lane, each instruction
+// 1 KB contiguous; the per-lane offset 16 lane is the P read's, the tile offset is scalar. (The key-major
+// [key][q] tile with four 8-byte stores and an offset register of its own spilled 20 bytes per lane.)
+template <int D, bool CAUSAL, bool EMIT_DS = false>
+__global__ void __launch_bounds__(512, 1)
+    attn_bwd_dkdv_w8_kernel(std::conditional_t<EMIT_DS, FastBwdWsParams, FastBwdParams> p) {
   constexpr int BK = 128, BQ = 32;
   constexpr int TILE = BQ * D * 2;            // one 32-row image
   using Stg = Stager<D, true, 512>;
@@ -1461,6 +1647,8 @@ __global__ void __launch_bounds__(512, 1) attn_bwd_dkdv_w8_kernel(FastBwdParams 
     }
     __syncthreads();  // step `total`: the K waves' last tile
   } else {
+    DsEmitter<EMIT_DS> emit;
+    emit.init(p, bh, lane, q_lo, kw);
     auto k_step = [&](int t, int cur, int nxt) {  // in step t + 1; nxt: buffer of tile t + 2
       const char* Qs = smem + cur * 2 * TILE;
       const char* Gs = Qs + TILE;
@@ -1505,6 +1693,7 @@ __global__ void __launch_bounds__(512, 1) attn_bwd_dkdv_w8_kernel(FastBwdParams 
           else s1[r - 8] = (__bf16)ds;
         }
       }
+      emit.store(s0, s1, t);
       ASTAMP(3);
       // dK^T += Q^T.dS, same rotation
       {
@@ -1563,11 +1752,14 @@ inline bool offsets_fit(long long rows, long long stride) { return (rows + 128) 
 }  // namespace
 
 // A/B knob for the full-tile kernels: bit 0 = 8-wave D = 256 forward (attn_fwd_w8_kernel),
-// bit 1 = 8-wave (two waves per SIMD) D = 256 dK/dV (attn_bwd_dkdv_w8_kernel; H == Hkv).
+// bit 1 = 8-wave (two waves per SIMD) D = 256 dK/dV (attn_bwd_dkdv_w8_kernel; H == Hkv),
+// bit 2 (with bit 1, through kca_attn_bwd_tiled_ws and a workspace) = that kernel writes dS and
+// attn_bwd_dq_ds_kernel computes dQ from it instead of recomputing S, dP and P.
 // (An LDS-DMA dQ kernel -- four buffers, three K/V tiles in flight, asm LDS reads -- measured
 // 1.5-2.5 % slower on GPT-J fwd+bwd than the register-staged one and was dropped.)
-// Both on by default (bit 1: GPT-J step 1910 -> 1879 ms same box, profiles/attn_dkdv_w8_ab_r7.jsonl).
-static int g_attn_variant = 3;
+// All three on by default (bit 1: GPT-J step 1910 -> 1879 ms same box, profiles/attn_dkdv_w8_ab_r7.jsonl;
+// bit 2: 1938 -> 1904 ms same box, profiles/attn_dq_ds_ab_r8.jsonl).
+static int g_attn_variant = 7;
 KCA_API int kca_attn_set_variant(int v) {
   g_attn_variant = v;
   return 0;
@@ -1710,6 +1902,49 @@ KCA_API int kca_attn_bwd_tiled(const void* q, const void* k, const void* v, cons
       hipLaunchKernelGGL((attn_bwd_dkdv_tiled_kernel<64, false>), g1, dim3(256), 0, stream, p);
       hipLaunchKernelGGL((attn_bwd_dq_tiled_kernel<64, false>), g2, dim3(256), 0, stream, p);
     }
+  }
+  return 0;
+}
+
+// Bytes of dS workspace the emit-and-consume backward (bit 2 of g_attn_variant) needs at this shape:
+// one bf16 per (b, h, q, key), addressed as 32-bit byte offsets per head. 0 = shape outside that path.
+KCA_API long long kca_attn_bwd_ws_bytes(int B, int Sq, int Sk, int H, int Hkv, int d, int causal) {
+  if (d != 256 || H != Hkv || B <= 0 || H <= 0 || Sq <= 0 || Sq % 128 || Sk % 128 || (causal && Sk < Sq)) return 0;
+  if ((long long)Sq * Sk * 2 >= (1ll << 31)) return 0;
+  return (long long)B * H * Sq * Sk * 2;
+}
+
+// kca_attn_bwd_tiled with a workspace: with bits 1 and 2 of g_attn_variant set, an eligible shape and
+// ws_bytes >= kca_attn_bwd_ws_bytes(..), the 8-wave dK/dV kernel emits dS and attn_bwd_dq_ds_kernel
+// computes dQ from it; otherwise exactly kca_attn_bwd_tiled.
+KCA_API int kca_attn_bwd_tiled_ws(const void* q, const void* k, const void* v, const void* dout,
+                                  void* dq, void* dk, void* dv, const float* lse, const float* delta,
+                                  long long q_sb, long long q_st, long long q_sh, long long k_sb,
+                                  long long k_st, long long k_sh, long long v_sb, long long v_st,
+                                  long long v_sh, long long do_sb, long long do_st, long long do_sh,
+                                  long long dq_sb, long long dq_st, long long dq_sh, long long dk_sb,
+                                  long long dk_st, long long dk_sh, long long dv_sb, long long dv_st,
+                                  long long dv_sh, int B, int Sq, int Sk, int H, int Hkv, int d,
+                                  int causal, float scale, void* ws, long long ws_bytes, hipStream_t stream) {
+  const long long need = kca_attn_bwd_ws_bytes(B, Sq, Sk, H, Hkv, d, causal);
+  if ((g_attn_variant & 6) != 6 || !ws || need == 0 || ws_bytes < need || !offsets_fit(Sk, k_st) ||
+      !offsets_fit(Sk, v_st) || !offsets_fit(Sq, q_st) || !offsets_fit(Sq, do_st))
+    return kca_attn_bwd_tiled(q, k, v, dout, dq, dk, dv, lse, delta, q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb,
+                              v_st, v_sh, do_sb, do_st, do_sh, dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb,
+                              dv_st, dv_sh, B, Sq, Sk, H, Hkv, d, causal, scale, stream);
+  FastBwdWsParams p{{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
+                     (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lse, delta,
+                     q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, do_sb, do_st, do_sh,
+                     dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb, dv_st, dv_sh,
+                     B, Sq, Sk, H, Hkv, scale},
+                    (bf16_t*)ws};
+  dim3 g1((Sk / 128) * B * H), g2((Sq / 128) * B * H);
+  if (causal) {
+    hipLaunchKernelGGL((attn_bwd_dkdv_w8_kernel<256, true, true>), g1, dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dq_ds_kernel<256, true>), g2, dim3(256), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dkdv_w8_kernel<256, false, true>), g1, dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dq_ds_kernel<256, false>), g2, dim3(256), 0, stream, p);
   }
   return 0;
 }

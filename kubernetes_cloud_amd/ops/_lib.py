@@ -69,6 +69,8 @@ _SIGS = {
     "kca_attn_fwd": [P] * 5 + [LL] * 12 + [I] * 7 + [F, P, P, I, P, I, I, P, P],
     "kca_attn_bwd_preprocess": [P, P, P, LL, LL, LL, LL, LL, LL, I, I, I, I, P],
     "kca_attn_bwd": [P] * 10 + [LL] * 21 + [I] * 7 + [F, P, P, I, P, P],
+    "kca_attn_bwd_ws": [P] * 10 + [LL] * 21 + [I] * 7 + [F, P, P, I, P, P, LL, P],
+    "kca_attn_bwd_ws_bytes": [I] * 7,
     "kca_attn_fwd_wide": [P] * 5 + [LL] * 12 + [I] * 6 + [F, P, P],
     "kca_attn_set_tiled": [I],
     "kca_attn_set_variant": [I],
@@ -118,6 +120,9 @@ _SIGS = {
 }
 
 
+# entry points that return a size, not a status
+_RESTYPES = {"kca_attn_bwd_ws_bytes": ctypes.c_longlong}
+
 # fused decode layer (batch 1): kca_decode_prep_attn's arguments (minus the stream), then the fc_in
 # GEMV's x, W, bias, y, N, K, act, then the stream
 _SIGS["kca_decode_prep_attn_gemv"] = _SIGS["kca_decode_prep_attn"][:-2] + [P, P, P, P, I, I, I, I, P]
@@ -148,7 +153,7 @@ def _load():
             if fn is None:
                 continue
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
+            fn.restype = _RESTYPES.get(name, ctypes.c_int)
         # KCA_ATTN_VARIANT=<bits>: the attention kernels' A/B knob (ops/attention.py set_variant), read
         # once here so a whole program (bench.py) can be A/B-ed from its environment
         if ATTN_VARIANT_ENV is not None and hasattr(lib, "kca_attn_set_variant"):

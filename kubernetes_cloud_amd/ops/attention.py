@@ -73,14 +73,17 @@ def set_tiled_path(enable: bool) -> None:
 
 # the library's built-in default (g_attn_variant, attention_tiled.hip), or KCA_ATTN_VARIANT, which
 # ops/_lib.py hands to the library once when it loads it
-DEFAULT_VARIANT = 3
+DEFAULT_VARIANT = 7
 _VARIANT = [int(_lib.ATTN_VARIANT_ENV) if _lib.ATTN_VARIANT_ENV is not None else DEFAULT_VARIANT]
 
 
 def set_variant(v: int) -> int:
     """Full-tile kernel variants (A/B knob, attention_tiled.hip): bit 0 = the 8-wave D = 256
-    forward (default on); bit 1 = the 8-wave, two-waves-per-SIMD D = 256 dK/dV kernel
-    (attn_bwd_dkdv_w8_kernel; H == Hkv, GQA keeps the 4-wave kernel). The environment variable
+    forward; bit 1 = the 8-wave, two-waves-per-SIMD D = 256 dK/dV kernel
+    (attn_bwd_dkdv_w8_kernel; H == Hkv, GQA keeps the 4-wave kernel); bit 2 (with bit 1, D = 256,
+    H == Hkv, and a workspace from ``bwd_workspace`` passed to ``_bwd``) = that kernel writes its dS
+    tiles to the workspace and attn_bwd_dq_ds_kernel computes dQ = dS.K from them instead of
+    recomputing S, dP and P (same bits; default on). The environment variable
     KCA_ATTN_VARIANT sets the initial value. Returns the previous value."""
     _lib.call("kca_attn_set_variant", int(v))
     old, _VARIANT[0] = _VARIANT[0], int(v)
@@ -128,18 +131,33 @@ def _fwd(q, k, v, causal, scale, kv_len, alibi, out=None, window: int = 0, rowsu
     return o, lse
 
 
-def _bwd(q, k, v, o, do, lse, dq, dk, dv, causal, scale, kv_len, alibi, window: int = 0):
+def bwd_workspace(q, k, causal):
+    """The uint8 dS workspace of the emit-and-consume backward (``set_variant`` bit 2) for q [B,Sq,H,D]
+    and k [B,Sk,Hkv,D], or None when the bit is off or the shape is outside that path. Not kept: the
+    caching allocator hands the same block to every layer's backward."""
+    if not _VARIANT[0] & 4:
+        return None
+    B, Sq, H, D = q.shape
+    n = _lib.require().kca_attn_bwd_ws_bytes(B, Sq, k.shape[1], H, k.shape[2], D, int(causal))
+    return torch.empty(n, device=q.device, dtype=torch.uint8) if n > 0 else None
+
+
+def _bwd(q, k, v, o, do, lse, dq, dk, dv, causal, scale, kv_len, alibi, window: int = 0, ws=None):
     B, Sq, H, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     delta = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     _lib.call("kca_attn_bwd_preprocess", o.data_ptr(), do.data_ptr(), delta.data_ptr(),
               *_strides(o), *_strides(do), B, Sq, H, D, _lib.stream())
-    _lib.call("kca_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
-              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-              *_strides(q), *_strides(k), *_strides(v), *_strides(do),
-              *_strides(dq), *_strides(dk), *_strides(dv),
-              B, Sq, Sk, H, Hkv, D, int(causal), float(scale), _lib.ptr(alibi), _lib.ptr(_masks(kv_len)[0]),
-              int(window), _lib.ptr(_masks(kv_len)[1]), _lib.stream())
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
+            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+            *_strides(q), *_strides(k), *_strides(v), *_strides(do),
+            *_strides(dq), *_strides(dk), *_strides(dv),
+            B, Sq, Sk, H, Hkv, D, int(causal), float(scale), _lib.ptr(alibi), _lib.ptr(_masks(kv_len)[0]),
+            int(window), _lib.ptr(_masks(kv_len)[1]))
+    if ws is None:
+        _lib.call("kca_attn_bwd", *args, _lib.stream())
+    else:
+        _lib.call("kca_attn_bwd_ws", *args, ws.data_ptr(), ws.numel() * ws.element_size(), _lib.stream())
 
 
 def _check(q, k, v):
@@ -169,7 +187,8 @@ class _FlashAttnFn(torch.autograd.Function):
         dq = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         dk = torch.empty(k.shape, device=k.device, dtype=k.dtype)
         dv = torch.empty(v.shape, device=v.device, dtype=v.dtype)
-        _bwd(q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale, kv_len, alibi, ctx.window)
+        _bwd(q, k, v, o, do, lse, dq, dk, dv, ctx.causal, ctx.scale, kv_len, alibi, ctx.window,
+             ws=bwd_workspace(q, k, ctx.causal))
         return dq, dk, dv, None, None, None, None, None
 
 
@@ -260,7 +279,7 @@ class _QKVRopeAttnFn(torch.autograd.Function):
         d5 = dqkv.view(B, S, 3, H, D)
         dq, dk, dv = d5[:, :, 0], d5[:, :, 1], d5[:, :, 2]
         do = do.contiguous().view(B, S, H, D)
-        _bwd(q, k, v, o, do, lse, dq, dk, dv, causal, scale, kv_len, None)
+        _bwd(q, k, v, o, do, lse, dq, dk, dv, causal, scale, kv_len, None, ws=bwd_workspace(q, k, causal))
         if rot > 0:
             apply_rotary_(dq, dk, rot, S, interleaved, base, -1.0)
         return dqkv, None, None, None, None, None, None, None, None

@@ -35,6 +35,7 @@ import torch.nn.functional as F
 from . import _lib, grad_sink
 from .attention import _bwd as _attn_bwd
 from .attention import _fwd as _attn_fwd
+from .attention import bwd_workspace as _attn_bwd_workspace
 from .attention import native_mask
 from .linear import transpose
 from .rope import apply_rotary_
@@ -159,7 +160,7 @@ class _FusedBlockFn(torch.autograd.Function):
         d5 = dqkv.view(B, S, 3, H, D)
         dq, dk, dv = d5[:, :, 0], d5[:, :, 1], d5[:, :, 2]
         _attn_bwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], o.view(B, S, H, D), do, lse, dq, dk, dv, True,
-                  a.scale, kv_len, None)
+                  a.scale, kv_len, None, ws=_attn_bwd_workspace(q5[:, :, 0], q5[:, :, 1], True))
         apply_rotary_(dq, dk, cfg.rotary_dim, S, cfg.rotary_interleaved, cfg.rotary_base, -1.0)
         del do
 

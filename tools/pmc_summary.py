@@ -37,6 +37,7 @@ CASE_OF = [
     (r"attn_bwd_dq_tiled_kernel<256", "attn_gptj", "bwd_flops_dq", None),
     (r"attn_bwd_dkdv_tiled_kernel<256", "attn_gptj", "bwd_flops_dkdv", None),
     (r"attn_bwd_dkdv_w8_kernel<256", "attn_gptj", "bwd_flops_dkdv", None),
+    (r"attn_bwd_dq_ds_kernel<256", "attn_gptj", "bwd_flops_dq_ds", None),
     (r"attn_fwd_tiled_kernel<64, false, -1, 48", "attn_sd_tiled48", "fwd_flops", None),
     (r"attn_bwd_dq_tiled_kernel<64, false, 48", "attn_sd_tiled48", "bwd_flops_dq", None),
     (r"attn_bwd_dkdv_tiled_kernel<64, false, 48", "attn_sd_tiled48", "bwd_flops_dkdv", None),
@@ -97,6 +98,7 @@ def main():
         if "bwd_flops" in c:
             c["bwd_flops_dq"] = c["bwd_flops"] * 2 / 5
             c["bwd_flops_dkdv"] = c["bwd_flops"] * 3 / 5
+            c["bwd_flops_dq_ds"] = c["bwd_flops"] / 5  # dQ = dS.K alone (variant bit 2)
     trace = {}
     for r in csv.DictReader(open(glob.glob(os.path.join(args.root, "trace", "*kernel_stats.csv"))[0])):
         trace[r["Name"]] = float(r["AverageNs"])
