@@ -23,6 +23,16 @@ travel in ONE packed pinned buffer -> one H2D copy. ``decode_async`` launches a
 step without waiting for it and can take each row's input token from the
 previous launch's device output, so the engine launches step t+1 before it
 reads step t's tokens (``LLMEngine``'s one-step lookahead).
+
+``weight_dtype="fp8"`` (or ``KCA_DECODE_WEIGHTS=fp8`` when the keyword is None;
+unset / ``0``: off, the default): FP8 weight-only decode. Every block's QKV,
+out-projection, fc_in and fc_out weights are quantized once at construction
+(``ops.w8.quantize_weight``: e4m3 bytes + one fp32 scale per output row) and every
+decode step takes the per-projection path with those four projections on
+``ln_rows`` + ``kca_w8_gemm``, streaming half the weight bytes. The LM head and
+the embeddings stay 16-bit. Prefill keeps using the 16-bit weights, so both copies
+stay resident: decode-time weight memory is 1.5x the 16-bit weights (2x with the
+default packed twins of the matrix-core layer, which this mode does not build).
 """
 from __future__ import annotations
 
@@ -36,6 +46,7 @@ from ..ops import decode as dops
 from ..ops import _lib
 from ..ops import skinny_mm as smm
 from ..ops.gemv import embed_ln_rows, ln_rows, ln_skinny_linear, skinny_linear
+from ..ops.w8 import quantize_weight, w8_linear
 
 # decode steps: each row's RoPE angles and page-table row travel with the step's packed inputs (fixed
 # device addresses), so every layer's attention chain loads them in its first memory round trip
@@ -311,7 +322,8 @@ class DecodeHandle:
 
 class ModelRunner:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
-                 max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None):
+                 max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None,
+                 weight_dtype: str | None = None):
         self.model = model.eval()
         cfg = model.cfg
         self.cfg = cfg
@@ -329,6 +341,8 @@ class ModelRunner:
         self.layer_devs = [blk.ln_1.weight.device for blk in model.h]
         self.head_dev = model.ln_f.weight.device
         self.multi_device = len({str(d) for d in self.layer_devs + [self.device, self.head_dev]}) > 1
+        self._w8 = self._quantize_decode_weights(weight_dtype)
+        self.w8_steps = 0  # decode steps built on the FP8 weights (eager runs and graph captures)
         self.cache = KVCache(cfg.n_layers, max_slots, self.Hkv, self.max_len, self.D, self.device, self.dtype,
                              page_size=page_size, n_pages=kv_pages, layer_devices=self.layer_devs)
         self.max_slots = max_slots
@@ -431,6 +445,30 @@ class ModelRunner:
         # BLOOM rank 13.38 vs 14.84 per-projection vs matrix-core layer (profiles/decode_fp16_cap_ab_r6.jsonl)
         self._batched_max_b = int(os.environ.get("KCA_DECODE_BATCHED_MAX_B", "0")) or \
             {"gptj": 16, "seq": 16}.get(self._layer_kind, 64)
+
+    def _quantize_decode_weights(self, weight_dtype):
+        """FP8 weight-only decode (module docstring): {id(linear): W8Weight} of every block's four
+        projections, or None with the option off."""
+        if weight_dtype is None:
+            weight_dtype = os.environ.get("KCA_DECODE_WEIGHTS", "") or None
+        if weight_dtype in (None, "0", "none", "off"):
+            return None
+        if weight_dtype != "fp8":
+            raise ValueError(f"weight_dtype / KCA_DECODE_WEIGHTS: {weight_dtype!r} (supported: 'fp8', or unset)")
+        from ..parallel import tensor_parallel as tpm
+        tp_types = tuple(t for t in (getattr(tpm, n, None) for n in
+                                     ("RowParallelLinear", "ColumnParallelLinear", "ParallelLMHead")) if t)
+        if any(isinstance(mm, tp_types) for mm in self.model.modules()):
+            raise ValueError("weight_dtype='fp8' (KCA_DECODE_WEIGHTS=fp8) does not cover tensor-parallel linears; "
+                             "serve this model with 16-bit weights")
+        if self.multi_device:
+            raise ValueError("weight_dtype='fp8' (KCA_DECODE_WEIGHTS=fp8) does not cover a layer-split placement; "
+                             "serve this model with 16-bit weights")
+        w8 = {}
+        for blk in self.model.h:
+            for mod in (blk.attn.qkv, blk.attn.out, blk.mlp.fc_in, blk.mlp.fc_out):
+                w8[id(mod)] = quantize_weight(mod.weight)
+        return w8
 
     # ------------------------------------------------------------- prefill
     @torch.no_grad()
@@ -774,12 +812,15 @@ class ModelRunner:
 
     def _layers_decode(self, tokens, pos, slots, kv_lens, max_kv, ws, obuf):
         m, cfg = self.model, self.cfg
-        if self._fused_ok and tokens.shape[0] == 1 and obuf is not None:
+        w8 = self._w8 is not None  # FP8 weights: the per-projection path at every batch size
+        self.w8_steps += w8
+        if not w8 and self._fused_ok and tokens.shape[0] == 1 and obuf is not None:
             y = self._layers_decode_fused(tokens, pos, slots, kv_lens, max_kv, ws, obuf)
             if y is not None:
                 self.fused_steps += 1
                 return y
-        if (self._batched_ok and 2 <= tokens.shape[0] <= min(smm.MAX_M, self._batched_max_b) and obuf is not None
+        if (not w8 and self._batched_ok and 2 <= tokens.shape[0] <= min(smm.MAX_M, self._batched_max_b)
+                and obuf is not None
                 and (self._chain_src is None or self._embed_head)):
             return self._layers_decode_batched(tokens, pos, slots, kv_lens, max_kv, ws, obuf)
         if self._chain_src is not None and obuf is not None:  # chained rows not resolved by a fused head
@@ -857,6 +898,10 @@ class ModelRunner:
         """LayerNorm(h + sum(res)) -> column-parallel / LM-head linear, fused (decode)."""
         from ..parallel.tensor_parallel import ParallelLMHead, RowParallelLinear, gather_last_dim
         assert not isinstance(mod, RowParallelLinear)
+        if self._w8 is not None and id(mod) in self._w8:  # FP8 weights: LayerNorm rows, then the e4m3 stream
+            xn, h = ln_rows(h, ln.weight, ln.bias, ln.eps, res)
+            y = w8_linear(xn, self._w8[id(mod)], mod.bias, act)
+            return (y, h, xn) if want_xn else (y, h)
         if isinstance(mod, ParallelLMHead):
             y, h = ln_skinny_linear(h, ln.weight, ln.bias, ln.eps, mod.local_weight(), mod.bias, res, act)
             return gather_last_dim(y, mod.group), h
@@ -866,6 +911,8 @@ class ModelRunner:
     # decode linears: skinny GEMM (W streamed once, bias/GELU fused) for <= 16 rows
     def _lin(self, mod, x, act: int = 0):
         from ..parallel.tensor_parallel import ParallelLMHead, RowParallelLinear, gather_last_dim, reduce_from_tp
+        if self._w8 is not None and id(mod) in self._w8:
+            return w8_linear(x, self._w8[id(mod)], mod.bias, act)
         if isinstance(mod, RowParallelLinear):
             y = reduce_from_tp(skinny_linear(x, mod.weight, None), mod.group)
             return y + mod.bias if mod.bias is not None else y

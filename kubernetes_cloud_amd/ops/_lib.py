@@ -95,6 +95,8 @@ _SIGS = {
     "kca_conv3x3_wgrad": [P, P, P, P, I, I, I, I, I, I, P],
     "kca_skinny_gemm": [P, LL, P, P, P, LL, I, I, I, I, P],
     "kca_skinny_set_splitk": [I],
+    "kca_w8_gemm": [P, LL, P, P, P, P, LL, I, I, I, I, I, P],
+    "kca_w8_set_kgroups": [I],
     "kca_mm_skinny_set": [I],
     "kca_ln_skinny_gemm": [P, LL, P, P, P, LL, P, P, F, P, P, P, LL, I, I, I, I, P, P],
     "kca_ln_rows": [P, LL, P, P, P, LL, P, P, F, P, I, I, P],
