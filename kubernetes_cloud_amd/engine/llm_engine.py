@@ -92,13 +92,17 @@ class LLMEngine:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_prefill_tokens: int = 16384, runner=None, page_size: int | None = None,
                  kv_pages: int | None = None, prefill_chunk: int | None = None, pipeline: bool | None = None,
-                 weight_dtype: str | None = None):
+                 weight_dtype: str | None = None, kv_dtype: str | None = None):
         # ``weight_dtype="fp8"``: FP8 weight-only decode (engine/runner.py; None reads KCA_DECODE_WEIGHTS)
+        # ``kv_dtype="fp8"``: FP8 KV cache (engine/runner.py; None reads KCA_DECODE_KV)
         # ``runner``: e.g. a tp_driver.CollectiveRunner that mirrors every call to TP follower ranks
         if runner is not None and weight_dtype is not None:
             raise ValueError("weight_dtype applies to the runner the engine builds; a supplied runner sets its own")
+        if runner is not None and kv_dtype is not None:
+            raise ValueError("kv_dtype applies to the runner the engine builds; a supplied runner sets its own")
         self.runner = runner or ModelRunner(model, max_slots=max_slots, max_len=max_len, use_graphs=use_graphs,
-                                            page_size=page_size, kv_pages=kv_pages, weight_dtype=weight_dtype)
+                                            page_size=page_size, kv_pages=kv_pages, weight_dtype=weight_dtype,
+                                            kv_dtype=kv_dtype)
         max_slots = self.runner.max_slots
         self.max_len = self.runner.max_len
         self.free = list(range(max_slots))[::-1]

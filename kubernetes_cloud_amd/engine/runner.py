@@ -33,6 +33,17 @@ decode step takes the per-projection path with those four projections on
 the embeddings stay 16-bit. Prefill keeps using the 16-bit weights, so both copies
 stay resident: decode-time weight memory is 1.5x the 16-bit weights (2x with the
 default packed twins of the matrix-core layer, which this mode does not build).
+
+``kv_dtype="fp8"`` (or ``KCA_DECODE_KV=fp8`` when the keyword is None; unset / ``0`` /
+``none`` / ``off``: off, the default): FP8 KV cache. Every cached K / V row is stored as
+e4m3 bytes plus one fp32 scale per (token, kv-head) (``ops.kv8``), (D + 4) / 2D of the
+16-bit cache, and every decode step takes the per-projection path with the attention on
+``kca_kv8_prep`` + ``kca_kv8_attn`` (``csrc/kernels/decode_kv8.hip``): the fused batch-1
+layer and the matrix-core layer are not used in this mode. Prefill attends to the 16-bit
+K / V of its own forward and quantizes only what it stores; chunked prefill sees the
+earlier chunks dequantized (quantized values) and the current chunk exact. Composes with
+``weight_dtype="fp8"``. Not covered: tensor-parallel and layer-split models, head dims
+outside D % 8 == 0, D <= 256, GQA groups other than 1 / 2 / 4 / 8 (``ValueError``).
 """
 from __future__ import annotations
 
@@ -46,6 +57,8 @@ from ..ops import decode as dops
 from ..ops import _lib
 from ..ops import skinny_mm as smm
 from ..ops.gemv import embed_ln_rows, ln_rows, ln_skinny_linear, skinny_linear
+from ..ops import kv8
+from ..ops.kv8 import quantize_rows
 from ..ops.w8 import quantize_weight, w8_linear
 
 # decode steps: each row's RoPE angles and page-table row travel with the step's packed inputs (fixed
@@ -81,11 +94,19 @@ class KVCache:
     the scratch page, so a stray read or a graph bucket's padding row touches
     nothing live. Head-major pages keep each (sequence, head, page) a
     contiguous PS*D*2-byte stream for the decode kernel (``ops.decode``).
+
+    ``kv_dtype="fp8"``: ``k`` / ``v`` hold OCP e4m3 bytes (uint8, the same shapes) and ``k_scale`` /
+    ``v_scale`` (fp32, ``shape[:-1]``) one scale per (token, kv-head) row (``ops.kv8``): (D + 4) / 2D of
+    the 16-bit cache's bytes. Pages, the block table, the scratch page / slot and ``fork`` work as above
+    (scales travel with their rows). The default (None) is the 16-bit cache, with no scale tensors.
     """
 
     def __init__(self, n_layers: int, slots: int, kv_heads: int, max_len: int, head_dim: int,
                  device, dtype=torch.bfloat16, page_size: int = 0, n_pages: int | None = None,
-                 layer_devices: list | None = None):
+                 layer_devices: list | None = None, kv_dtype: str | None = None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"KVCache kv_dtype: {kv_dtype!r} (supported: 'fp8', or None)")
+        self.kv_dtype = kv_dtype
         self.slots, self.max_len, self.scratch = slots, max_len, slots
         self.page_size = page_size
         self.device = torch.device(device)
@@ -113,11 +134,24 @@ class KVCache:
             self.n_pages = 0
             shape = (slots + 1, kv_heads, max_len, head_dim)
             self.tables = {}
+        self.dtype = dtype  # the model's element type (an FP8 cache dequantizes to it for chunked prefill)
+        if kv_dtype == "fp8":
+            dtype = torch.uint8
         self.k = [torch.zeros(shape, device=d, dtype=dtype) for d in self.layer_devices]
         self.v = [torch.zeros(shape, device=d, dtype=dtype) for d in self.layer_devices]
+        self.k_scale = self.v_scale = None
+        if kv_dtype == "fp8":
+            self.k_scale = [torch.zeros(shape[:-1], device=d, dtype=torch.float32) for d in self.layer_devices]
+            self.v_scale = [torch.zeros(shape[:-1], device=d, dtype=torch.float32) for d in self.layer_devices]
+
+    def _tensors(self):
+        """Per layer, the tensors that hold its rows: (k, v) or (k, v, k_scale, v_scale)."""
+        if self.k_scale is None:
+            return list(zip(self.k, self.v))
+        return list(zip(self.k, self.v, self.k_scale, self.v_scale))
 
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.k + self.v)
+        return sum(t.numel() * t.element_size() for ts in self._tensors() for t in ts)
 
     @property
     def paged(self) -> bool:
@@ -184,9 +218,9 @@ class KVCache:
             return
         if not self.paged:
             d, s = self._per_layer(dst), self._per_layer(src)
-            for k, v, dev in zip(self.k, self.v, self.layer_devices):
-                k[d[dev], :, :upto] = k[s[dev], :, :upto]  # RHS gathered first: overlapping permutations are safe
-                v[d[dev], :, :upto] = v[s[dev], :, :upto]
+            for ts, dev in zip(self._tensors(), self.layer_devices):
+                for t in ts:  # (FP8: the scales of the prefix with its rows)
+                    t[d[dev], :, :upto] = t[s[dev], :, :upto]  # RHS gathered first: overlapping permutations are safe
             return
         full, part = divmod(upto, self.page_size)
         new_lists, cp_from, cp_to = [], [], []
@@ -207,9 +241,9 @@ class KVCache:
             new_lists.append(lst)
         if cp_to:
             a, b = self._per_layer(cp_from), self._per_layer(cp_to)
-            for k, v, dev in zip(self.k, self.v, self.layer_devices):
-                k[b[dev]] = k[a[dev]]
-                v[b[dev]] = v[a[dev]]
+            for ts, dev in zip(self._tensors(), self.layer_devices):
+                for t in ts:  # (FP8: the tail page's scales with its rows)
+                    t[b[dev]] = t[a[dev]]
         for d_, lst in zip(dst, new_lists):  # old dst pages go only after every source was read
             self._drop(self.pages[d_])
             self.pages[d_] = lst
@@ -239,8 +273,22 @@ class KVCache:
 
     def write(self, li: int, k: torch.Tensor, v: torch.Tensor, slots: list[int], lens: list[int], plan,
               start: list[int] | None = None):
-        """k, v: [n, T, Hkv, D] (strided views of the QKV GEMM output)."""
+        """k, v: [n, T, Hkv, D] (strided views of the QKV GEMM output). FP8 cache: the rows are
+        quantized here in torch (``ops.kv8.quantize_rows``; prefill is not the hot path) and bytes and
+        scales take the same plan."""
         kc, vc = self.k[li], self.v[li]
+        if self.k_scale is not None:
+            (k, ks), (v, vs) = quantize_rows(k), quantize_rows(v)
+            ksc, vsc = self.k_scale[li], self.v_scale[li]
+            if plan is None:
+                start = start or [0] * len(slots)
+                for i, (s_, L, p0) in enumerate(zip(slots, lens, start)):
+                    ksc[s_, :, p0:p0 + L].copy_(ks[i, :L].transpose(0, 1))
+                    vsc[s_, :, p0:p0 + L].copy_(vs[i, :L].transpose(0, 1))
+            else:
+                pg, off, src = plan[self.layer_devices[li]]
+                ksc[pg, :, off] = ks.reshape(-1, ks.shape[-1])[src]
+                vsc[pg, :, off] = vs.reshape(-1, vs.shape[-1])[src]
         if plan is None:
             start = start or [0] * len(slots)
             for i, (s_, L, p0) in enumerate(zip(slots, lens, start)):  # strided copies (index scatter is ~4x slower)
@@ -323,7 +371,7 @@ class DecodeHandle:
 class ModelRunner:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None,
-                 weight_dtype: str | None = None):
+                 weight_dtype: str | None = None, kv_dtype: str | None = None):
         self.model = model.eval()
         cfg = model.cfg
         self.cfg = cfg
@@ -343,8 +391,11 @@ class ModelRunner:
         self.multi_device = len({str(d) for d in self.layer_devs + [self.device, self.head_dev]}) > 1
         self._w8 = self._quantize_decode_weights(weight_dtype)
         self.w8_steps = 0  # decode steps built on the FP8 weights (eager runs and graph captures)
+        self._kv8 = self._kv_dtype(kv_dtype) == "fp8"
+        self.kv8_steps = 0  # decode steps built on the FP8 KV cache (eager runs and graph captures)
         self.cache = KVCache(cfg.n_layers, max_slots, self.Hkv, self.max_len, self.D, self.device, self.dtype,
-                             page_size=page_size, n_pages=kv_pages, layer_devices=self.layer_devs)
+                             page_size=page_size, n_pages=kv_pages, layer_devices=self.layer_devs,
+                             kv_dtype="fp8" if self._kv8 else None)
         self.max_slots = max_slots
         self.rot = cfg.rotary_dim
         self._rope = {}
@@ -446,6 +497,29 @@ class ModelRunner:
         self._batched_max_b = int(os.environ.get("KCA_DECODE_BATCHED_MAX_B", "0")) or \
             {"gptj": 16, "seq": 16}.get(self._layer_kind, 64)
 
+    def _kv_dtype(self, kv_dtype):
+        """FP8 KV cache (module docstring): "fp8" or None, from the keyword or KCA_DECODE_KV."""
+        if kv_dtype is None:
+            kv_dtype = os.environ.get("KCA_DECODE_KV", "") or None
+        if kv_dtype in (None, "0", "none", "off"):
+            return None
+        if kv_dtype != "fp8":
+            raise ValueError(f"kv_dtype / KCA_DECODE_KV: {kv_dtype!r} (supported: 'fp8', or unset)")
+        from ..parallel import tensor_parallel as tpm
+        tp_types = tuple(t for t in (getattr(tpm, n, None) for n in
+                                     ("RowParallelLinear", "ColumnParallelLinear", "ParallelLMHead")) if t)
+        if any(isinstance(mm, tp_types) for mm in self.model.modules()):
+            raise ValueError("kv_dtype='fp8' (KCA_DECODE_KV=fp8) does not cover tensor-parallel models; "
+                             "serve this model with the 16-bit KV cache")
+        if self.multi_device:
+            raise ValueError("kv_dtype='fp8' (KCA_DECODE_KV=fp8) does not cover a layer-split placement; "
+                             "serve this model with the 16-bit KV cache")
+        if not kv8.supported(self.D, self.H, self.Hkv):
+            raise ValueError(f"kv_dtype='fp8' (KCA_DECODE_KV=fp8) does not cover head_dim {self.D} with "
+                             f"{self.H} query / {self.Hkv} KV heads (needs head_dim % 8 == 0, <= 256, and "
+                             f"{kv8.GROUPS} query heads per KV head); serve this model with the 16-bit KV cache")
+        return "fp8"
+
     def _quantize_decode_weights(self, weight_dtype):
         """FP8 weight-only decode (module docstring): {id(linear): W8Weight} of every block's four
         projections, or None with the option off."""
@@ -527,7 +601,7 @@ class ModelRunner:
                                   pos_ids=pos_ids, max_pos=self.max_len)
             self.cache.write(li, k, v, slots, lens, plan, start)
             if cont:
-                o = self._continued_attention(li, q, slots, lens, start, at)
+                o = self._continued_attention(li, q, slots, lens, start, at, cur=(k, v))
             else:  # (GPT-Neo local layers: banded, the kernels skip the tiles left of the band)
                 o = ops.flash_attention(q, k, v, causal=True, scale=at.scale, alibi=at.alibi, window=at.window)
             a = at.out(o.reshape(n, T, -1))
@@ -548,18 +622,28 @@ class ModelRunner:
         y, _ = m.ln_f(pick(h), residual=tuple(pick(p_) for p_ in pending))
         return m.logits_from_hidden(y)[:, -1].to(self.device)
 
-    def _continued_attention(self, li, q, slots, lens, start, at):
+    def _continued_attention(self, li, q, slots, lens, start, at, cur=None):
         """Chunk queries [start, start + L) of each row against the slot's cached
         keys [0, start + L) (just written): bottom-right-aligned causal mask,
-        so query j of the chunk sees keys <= start + j."""
+        so query j of the chunk sees keys <= start + j. FP8 KV cache: the gathered window is
+        dequantized to the model dtype, so the earlier chunks are seen as stored (quantized) and the
+        current chunk exact (its own 16-bit K / V, not what was just written)."""
         n, T = q.shape[0], q.shape[1]
         o = torch.zeros_like(q)
         kc, vc, tbl = self.cache.k[li], self.cache.v[li], self.cache.table_on(self.layer_devs[li])
         for i, (s_, L, p0) in enumerate(zip(slots, lens, start)):
             kv = p0 + L
             lo = max(0, kv - L - at.window + 1) if at.window else 0  # oldest key any chunk query can see
-            kw = dops.gather_kv(kc, s_, kv, tbl)[:, lo:].transpose(0, 1)[None]
-            vw = dops.gather_kv(vc, s_, kv, tbl)[:, lo:].transpose(0, 1)[None]
+            if self._kv8:
+                ksc, vsc = self.cache.k_scale[li], self.cache.v_scale[li]
+                kw, vw = cur[0][i, :L], cur[1][i, :L]
+                if p0 > 0:
+                    kw = torch.cat((kv8.gather_kv8(kc, ksc, s_, p0, tbl, q.dtype).transpose(0, 1), kw))
+                    vw = torch.cat((kv8.gather_kv8(vc, vsc, s_, p0, tbl, q.dtype).transpose(0, 1), vw))
+                kw, vw = kw[lo:][None], vw[lo:][None]
+            else:
+                kw = dops.gather_kv(kc, s_, kv, tbl)[:, lo:].transpose(0, 1)[None]
+                vw = dops.gather_kv(vc, s_, kv, tbl)[:, lo:].transpose(0, 1)[None]
             o[i:i + 1, :L] = ops.flash_attention(q[i:i + 1, :L], kw, vw, causal=True, scale=at.scale,
                                                  alibi=at.alibi, window=at.window)
         return o
@@ -814,6 +898,8 @@ class ModelRunner:
         m, cfg = self.model, self.cfg
         w8 = self._w8 is not None  # FP8 weights: the per-projection path at every batch size
         self.w8_steps += w8
+        self.kv8_steps += self._kv8
+        w8 = w8 or self._kv8  # FP8 KV cache: the per-projection path too (its attention is its own launches)
         if not w8 and self._fused_ok and tokens.shape[0] == 1 and obuf is not None:
             y = self._layers_decode_fused(tokens, pos, slots, kv_lens, max_kv, ws, obuf)
             if y is not None:
@@ -865,13 +951,19 @@ class ModelRunner:
             kc, vc, tbl = self.cache.k[li], self.cache.v[li], self.cache.table_on(dev)
             cos, sin = self._rope[dev]
             by_row = 0
-            if obuf is not None and not self.multi_device:  # a graph-bucket step: its descriptors
+            if obuf is not None and not self.multi_device and not self._kv8:  # a graph-bucket step: its descriptors
                 cos, sin, tbl, by_row = self._desc_args(cos, sin, tbl)
             # RoPE + cache append + split-K attention (one launch on the GPU; GPT-Neo local layers read
             # only the last `window` positions)
-            o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
-                                           cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
-                                           out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+            if self._kv8:  # FP8 KV cache: quantizing prep, attention over the bytes (+ combine past one split)
+                o = kv8.kv8_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
+                                           cos, sin, pos, slots, kc, vc, self.cache.k_scale[li],
+                                           self.cache.v_scale[li], kv_lens, max_kv, at.scale, at.alibi,
+                                           out=obuf, ws=ws, block_table=tbl, window=at.window)
+            else:
+                o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
+                                               cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
+                                               out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
             a = self._lin(at.out, o)
             if side_out is not None:  # join
                 cur.wait_stream(self._side)

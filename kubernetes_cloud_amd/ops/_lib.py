@@ -97,6 +97,10 @@ _SIGS = {
     "kca_skinny_set_splitk": [I],
     "kca_w8_gemm": [P, LL, P, P, P, P, LL, I, I, I, I, I, P],
     "kca_w8_set_kgroups": [I],
+    # FP8 KV cache (csrc/kernels/decode_kv8.hip); the last int before the stream is dt (0 bf16, 1 fp16)
+    "kca_kv8_prep": [P, LL, I, I, I, I, I, I, P, P, P, P, P, P, P, P, LL, LL, LL, LL, LL, P, I, I, I, P],
+    "kca_kv8_attn": [P, LL, P, P, P, P, LL, LL, LL, LL, LL, P, P, P, LL, P, LL, I, I, I, I, I, I, F, P, P, I, I, I,
+                     I, P],
     "kca_mm_skinny_set": [I],
     "kca_ln_skinny_gemm": [P, LL, P, P, P, LL, P, P, F, P, P, P, LL, I, I, I, I, P, P],
     "kca_ln_rows": [P, LL, P, P, P, LL, P, P, F, P, I, I, P],

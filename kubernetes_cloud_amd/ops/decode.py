@@ -44,6 +44,19 @@ def decode_prep(qkv: torch.Tensor, n_heads: int, kv_heads: int, head_dim: int, r
                   v_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), tbl, tstride, shift,
                   _lib.stream())
         return
+    x = _prep_rows_reference(qkv, H, Hkv, D, rot, interleaved, cos, sin, pos)
+    sl, p = slots.long(), pos.long()
+    if block_table is not None:
+        PS = k_cache.shape[2]
+        sl, p = block_table.long()[sl, p // PS], p % PS
+    k_cache[sl, :, p] = x[:, H:H + Hkv].to(k_cache.dtype)
+    v_cache[sl, :, p] = x[:, H + Hkv:].to(v_cache.dtype)
+
+
+def _prep_rows_reference(qkv, H, Hkv, D, rot, interleaved, cos, sin, pos):
+    """The reference rotation of ``decode_prep`` (and of ``ops.kv8.kv8_prep_reference``): Q rotated in
+    place in ``qkv``; returns the fp32 head rows [B, H + 2 Hkv, D] with Q and K rotated."""
+    B = qkv.shape[0]
     rows = qkv.view(B, H + 2 * Hkv, D)
     x = rows.to(torch.float32, copy=True)  # never alias: K rows of qkv stay unrotated
     if rot > 0:
@@ -59,12 +72,7 @@ def decode_prep(qkv: torch.Tensor, n_heads: int, kv_heads: int, head_dim: int, r
             out = torch.cat((a * c - b * s, b * c + a * s), dim=-1)
         x[:, :H + Hkv, :rot] = out
         rows[:, :H, :rot] = x[:, :H, :rot].to(rows.dtype)
-    sl, p = slots.long(), pos.long()
-    if block_table is not None:
-        PS = k_cache.shape[2]
-        sl, p = block_table.long()[sl, p // PS], p % PS
-    k_cache[sl, :, p] = x[:, H:H + Hkv].to(k_cache.dtype)
-    v_cache[sl, :, p] = x[:, H + Hkv:].to(v_cache.dtype)
+    return x
 
 
 def _table_args(block_table, k_cache):
