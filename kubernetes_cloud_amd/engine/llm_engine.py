@@ -93,7 +93,8 @@ class LLMEngine:
                  max_prefill_tokens: int = 16384, runner=None, page_size: int | None = None,
                  kv_pages: int | None = None, prefill_chunk: int | None = None, pipeline: bool | None = None,
                  weight_dtype: str | None = None, kv_dtype: str | None = None):
-        # ``weight_dtype="fp8"``: FP8 weight-only decode (engine/runner.py; None reads KCA_DECODE_WEIGHTS)
+        # ``weight_dtype="fp8"`` / ``"mxfp4"``: FP8 / MXFP4 weight-only decode (engine/runner.py; None reads
+        # KCA_DECODE_WEIGHTS)
         # ``kv_dtype="fp8"``: FP8 KV cache (engine/runner.py; None reads KCA_DECODE_KV)
         # ``runner``: e.g. a tp_driver.CollectiveRunner that mirrors every call to TP follower ranks
         if runner is not None and weight_dtype is not None:

@@ -34,6 +34,16 @@ the embeddings stay 16-bit. Prefill keeps using the 16-bit weights, so both copi
 stay resident: decode-time weight memory is 1.5x the 16-bit weights (2x with the
 default packed twins of the matrix-core layer, which this mode does not build).
 
+``weight_dtype="mxfp4"`` (``KCA_DECODE_WEIGHTS=mxfp4``): MXFP4 weight-only decode, the same
+scheme one format further. The four projections of every block are quantized once
+(``ops.mx4.quantize_weight``: e2m1 nibbles + one e8m0 scale byte per 32 consecutive
+``k`` of an output row, 0.53 bytes per weight) and every decode step at every batch
+size takes the per-projection path on ``ln_rows`` + ``kca_mx4_gemm``
+(``csrc/kernels/gemv_mx4.hip``); ``mx4_steps`` counts those steps, and ``w8_steps``,
+``fused_steps`` and ``batched_steps`` stay 0. The LM head, the embeddings and prefill
+keep 16-bit weights. Composes with ``kv_dtype="fp8"``. Not covered: tensor-parallel
+linears, layer-split placement, a projection with ``K % 32 != 0`` (``ValueError``).
+
 ``kv_dtype="fp8"`` (or ``KCA_DECODE_KV=fp8`` when the keyword is None; unset / ``0`` /
 ``none`` / ``off``: off, the default): FP8 KV cache. Every cached K / V row is stored as
 e4m3 bytes plus one fp32 scale per (token, kv-head) (``ops.kv8``), (D + 4) / 2D of the
@@ -59,6 +69,7 @@ from ..ops import skinny_mm as smm
 from ..ops.gemv import embed_ln_rows, ln_rows, ln_skinny_linear, skinny_linear
 from ..ops import kv8
 from ..ops.kv8 import quantize_rows
+from ..ops import mx4
 from ..ops.w8 import quantize_weight, w8_linear
 
 # decode steps: each row's RoPE angles and page-table row travel with the step's packed inputs (fixed
@@ -389,8 +400,9 @@ class ModelRunner:
         self.layer_devs = [blk.ln_1.weight.device for blk in model.h]
         self.head_dev = model.ln_f.weight.device
         self.multi_device = len({str(d) for d in self.layer_devs + [self.device, self.head_dev]}) > 1
-        self._w8 = self._quantize_decode_weights(weight_dtype)
+        self._w8, self._mx4 = self._quantize_decode_weights(weight_dtype)
         self.w8_steps = 0  # decode steps built on the FP8 weights (eager runs and graph captures)
+        self.mx4_steps = 0  # ... on the MXFP4 weights
         self._kv8 = self._kv_dtype(kv_dtype) == "fp8"
         self.kv8_steps = 0  # decode steps built on the FP8 KV cache (eager runs and graph captures)
         self.cache = KVCache(cfg.n_layers, max_slots, self.Hkv, self.max_len, self.D, self.device, self.dtype,
@@ -521,28 +533,35 @@ class ModelRunner:
         return "fp8"
 
     def _quantize_decode_weights(self, weight_dtype):
-        """FP8 weight-only decode (module docstring): {id(linear): W8Weight} of every block's four
-        projections, or None with the option off."""
+        """Weight-only decode (module docstring): ``({id(linear): W8Weight} | None, {id(linear):
+        MX4Weight} | None)`` of every block's four projections -- FP8, MXFP4, or both None with the
+        option off."""
         if weight_dtype is None:
             weight_dtype = os.environ.get("KCA_DECODE_WEIGHTS", "") or None
         if weight_dtype in (None, "0", "none", "off"):
-            return None
-        if weight_dtype != "fp8":
-            raise ValueError(f"weight_dtype / KCA_DECODE_WEIGHTS: {weight_dtype!r} (supported: 'fp8', or unset)")
+            return None, None
+        if weight_dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype / KCA_DECODE_WEIGHTS: {weight_dtype!r} "
+                             "(supported: 'fp8', 'mxfp4', or unset)")
+        opt = f"weight_dtype='{weight_dtype}' (KCA_DECODE_WEIGHTS={weight_dtype})"
         from ..parallel import tensor_parallel as tpm
         tp_types = tuple(t for t in (getattr(tpm, n, None) for n in
                                      ("RowParallelLinear", "ColumnParallelLinear", "ParallelLMHead")) if t)
         if any(isinstance(mm, tp_types) for mm in self.model.modules()):
-            raise ValueError("weight_dtype='fp8' (KCA_DECODE_WEIGHTS=fp8) does not cover tensor-parallel linears; "
+            raise ValueError(f"{opt} does not cover tensor-parallel linears; "
                              "serve this model with 16-bit weights")
         if self.multi_device:
-            raise ValueError("weight_dtype='fp8' (KCA_DECODE_WEIGHTS=fp8) does not cover a layer-split placement; "
+            raise ValueError(f"{opt} does not cover a layer-split placement; "
                              "serve this model with 16-bit weights")
-        w8 = {}
-        for blk in self.model.h:
-            for mod in (blk.attn.qkv, blk.attn.out, blk.mlp.fc_in, blk.mlp.fc_out):
-                w8[id(mod)] = quantize_weight(mod.weight)
-        return w8
+        mods = [mod for blk in self.model.h for mod in (blk.attn.qkv, blk.attn.out, blk.mlp.fc_in, blk.mlp.fc_out)]
+        if weight_dtype == "fp8":
+            return {id(mod): quantize_weight(mod.weight) for mod in mods}, None
+        for mod in mods:
+            if mod.weight.shape[1] % mx4.BLOCK:
+                raise ValueError(f"{opt} does not cover a projection with K = {mod.weight.shape[1]} "
+                                 f"(MXFP4 blocks are {mx4.BLOCK} wide: K % {mx4.BLOCK} == 0); "
+                                 "serve this model with 16-bit weights")
+        return None, {id(mod): mx4.quantize_weight(mod.weight) for mod in mods}
 
     # ------------------------------------------------------------- prefill
     @torch.no_grad()
@@ -898,8 +917,9 @@ class ModelRunner:
         m, cfg = self.model, self.cfg
         w8 = self._w8 is not None  # FP8 weights: the per-projection path at every batch size
         self.w8_steps += w8
+        self.mx4_steps += self._mx4 is not None
         self.kv8_steps += self._kv8
-        w8 = w8 or self._kv8  # FP8 KV cache: the per-projection path too (its attention is its own launches)
+        w8 = w8 or self._mx4 is not None or self._kv8  # MXFP4 weights likewise; FP8 KV cache: the per-projection path too (its attention is its own launches)
         if not w8 and self._fused_ok and tokens.shape[0] == 1 and obuf is not None:
             y = self._layers_decode_fused(tokens, pos, slots, kv_lens, max_kv, ws, obuf)
             if y is not None:
@@ -994,6 +1014,10 @@ class ModelRunner:
             xn, h = ln_rows(h, ln.weight, ln.bias, ln.eps, res)
             y = w8_linear(xn, self._w8[id(mod)], mod.bias, act)
             return (y, h, xn) if want_xn else (y, h)
+        if self._mx4 is not None and id(mod) in self._mx4:  # MXFP4 weights: the same, on the nibble stream
+            xn, h = ln_rows(h, ln.weight, ln.bias, ln.eps, res)
+            y = mx4.mx4_linear(xn, self._mx4[id(mod)], mod.bias, act)
+            return (y, h, xn) if want_xn else (y, h)
         if isinstance(mod, ParallelLMHead):
             y, h = ln_skinny_linear(h, ln.weight, ln.bias, ln.eps, mod.local_weight(), mod.bias, res, act)
             return gather_last_dim(y, mod.group), h
@@ -1005,6 +1029,8 @@ class ModelRunner:
         from ..parallel.tensor_parallel import ParallelLMHead, RowParallelLinear, gather_last_dim, reduce_from_tp
         if self._w8 is not None and id(mod) in self._w8:
             return w8_linear(x, self._w8[id(mod)], mod.bias, act)
+        if self._mx4 is not None and id(mod) in self._mx4:
+            return mx4.mx4_linear(x, self._mx4[id(mod)], mod.bias, act)
         if isinstance(mod, RowParallelLinear):
             y = reduce_from_tp(skinny_linear(x, mod.weight, None), mod.group)
             return y + mod.bias if mod.bias is not None else y
