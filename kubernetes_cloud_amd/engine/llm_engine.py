@@ -28,7 +28,17 @@ Admission reserves a request's worst-case page count (prompt + max_new_tokens)
 against the paged cache, so a running request never runs out of pages (no
 preemption needed); pages go back to the pool the step a request finishes.
 Admitted prompts of different lengths prefill together, right-padded into a
-few length-sorted batches (``_prefill_groups``). ``start()`` runs
+few length-sorted batches (``_prefill_groups``).
+Speculative decoding (``spec_tokens=T``, or ``KCA_DECODE_SPEC=T`` in the environment; off by default):
+every step a proposer (``engine.spec.NgramProposer`` unless one is given) drafts up to T - 1 tokens per
+running request and ``ModelRunner.verify`` samples all T positions in one pass over the weights. With
+samples s_0..s_{n-1} of drafts d_1..d_{n-1} the request takes s_0, then s_t while s_{t-1} == d_t: each
+token is sampled from the model's own distribution given a prefix that is already confirmed, with the
+seed and the bans of its position, so greedy and seeded sampled outputs are what they are without
+speculation. Drafts never reach past the request's ``max_new_tokens`` / ``max_len``, so the admission's
+page count stays exact. A request with a repetition penalty or a multi-token bad word, or without a
+proposal, rides along with one token; a step in which nobody has a draft is an ordinary decode step.
+The one-step lookahead is off while speculation is on. ``start()`` runs
 the loop on a background thread for the HTTP servers; ``generate()`` is the
 synchronous batch API used by the finetuner sampler and the evaluator.
 """
@@ -92,7 +102,10 @@ class LLMEngine:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_prefill_tokens: int = 16384, runner=None, page_size: int | None = None,
                  kv_pages: int | None = None, prefill_chunk: int | None = None, pipeline: bool | None = None,
-                 weight_dtype: str | None = None, kv_dtype: str | None = None):
+                 weight_dtype: str | None = None, kv_dtype: str | None = None,
+                 spec_tokens: int | str | None = None, proposer=None):
+        # ``spec_tokens=T`` (2 / 4 / 8): speculative decoding (module docstring; None reads KCA_DECODE_SPEC);
+        # ``proposer``: an object with ``propose(tokens, k) -> list[int]`` (default: engine.spec.NgramProposer)
         # ``weight_dtype="fp8"`` / ``"mxfp4"``: FP8 / MXFP4 weight-only decode (engine/runner.py; None reads
         # KCA_DECODE_WEIGHTS)
         # ``kv_dtype="fp8"``: FP8 KV cache (engine/runner.py; None reads KCA_DECODE_KV)
@@ -101,9 +114,20 @@ class LLMEngine:
             raise ValueError("weight_dtype applies to the runner the engine builds; a supplied runner sets its own")
         if runner is not None and kv_dtype is not None:
             raise ValueError("kv_dtype applies to the runner the engine builds; a supplied runner sets its own")
+        if runner is not None and spec_tokens is not None:
+            raise ValueError("spec_tokens applies to the runner the engine builds; a supplied runner sets its own")
         self.runner = runner or ModelRunner(model, max_slots=max_slots, max_len=max_len, use_graphs=use_graphs,
                                             page_size=page_size, kv_pages=kv_pages, weight_dtype=weight_dtype,
-                                            kv_dtype=kv_dtype)
+                                            kv_dtype=kv_dtype, spec_tokens=spec_tokens)
+        self.spec_tokens = int(getattr(self.runner, "spec_tokens", 0) or 0)
+        if self.spec_tokens and pipeline:
+            raise ValueError("pipeline=True (one-step lookahead) does not combine with speculative decoding")
+        if proposer is not None and not callable(getattr(proposer, "propose", None)):
+            raise ValueError("proposer needs a propose(tokens, k) -> list[int] method")
+        if self.spec_tokens and proposer is None:
+            from .spec import NgramProposer
+            proposer = NgramProposer()
+        self.proposer = proposer
         max_slots = self.runner.max_slots
         self.max_len = self.runner.max_len
         self.free = list(range(max_slots))[::-1]
@@ -120,10 +144,12 @@ class LLMEngine:
         self.prefill_chunk = int(prefill_chunk) if prefill_chunk else 0
         self.prefilling: list[Request] = []  # admitted, prompt partially in the cache (r.prefilled tokens)
         self.pipeline = bool(getattr(self.runner, "pipelined", False)) if pipeline is None else pipeline
+        if self.spec_tokens:
+            self.pipeline = False
         self._inflight = None  # (DecodeHandle, [Request]) of the launched, not yet read decode step
         self.stats = {"steps": 0, "decode_tokens": 0, "prefill_tokens": 0, "finished": 0, "prefill_batches": 0,
                       "prefill_pad_tokens": 0, "prefill_chunks": 0, "max_step_prefill_tokens": 0,
-                      "decode_steps": 0}
+                      "decode_steps": 0, "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         cache = getattr(self.runner, "cache", None)
         self._paged = cache is not None and getattr(cache, "paged", False)
         self._page_budget = cache.n_pages if self._paged else 0
@@ -338,7 +364,9 @@ class LLMEngine:
             # the drained step may have finished requests (slot released, pages freed)
             self.running = [r for r in self.running if not r.done]
             rows = [self._row(r) for r in self.running]
-            if rows:
+            if rows and self.spec_tokens and self._decode_spec(rows, finished):
+                pass
+            elif rows:
                 toks, lps = self.runner.decode(rows)
                 self.stats["decode_tokens"] += len(rows)
                 self.stats["decode_steps"] += 1
@@ -357,6 +385,51 @@ class LLMEngine:
             if r.done:
                 self._finish(r)
                 finished.append(r)
+
+    # ---------------------------------------------------------- speculation
+    def _drafts(self, r: Request) -> list:
+        """Up to T - 1 drafted tokens for ``r``: none for a request the verify step does not cover, and
+        never more than it may still generate after this step's own token."""
+        p = r.params
+        k = min(self.spec_tokens - 1, p.max_new_tokens - len(r.output) - 1, self.max_len - len(r.tokens) - 1)
+        if k <= 0 or (p.repetition_penalty or 1.0) != 1.0 or any(len(w) > 1 for w in (p.bad_words_ids or ())):
+            return []
+        return [int(t) for t in self.proposer.propose(r.tokens, k)][:k]
+
+    def _decode_spec(self, rows: list, finished) -> bool:
+        """Draft and verify for the running requests (``rows``: their decode rows). False -- nothing
+        launched -- when no request has a draft: the caller runs the ordinary decode step."""
+        drafts = [self._drafts(r) for r in self.running]
+        if not any(drafts):
+            return False
+        vrows = []
+        for r, row, d in zip(self.running, rows, drafts):
+            p, n_gen = r.params, len(r.output)
+            single = [int(w[0]) for w in (p.bad_words_ids or ()) if len(w) == 1]
+            bans = [row["bans"]]
+            for t in range(1, len(d) + 1):  # position t's own bans: it is the (n_gen + t)-th new token
+                eos = p.eos_token_id is not None and n_gen + t < p.min_new_tokens
+                bans.append(single + ([int(p.eos_token_id)] if eos else []))
+            vrows.append({"tokens": [row["token"]] + d, "pos": row["pos"], "slot": row["slot"],
+                          "temperature": row["temperature"], "top_k": row["top_k"], "top_p": row["top_p"],
+                          "rep": row["rep"], "seeds": [mix_seed(r.seed, n_gen + t) for t in range(len(d) + 1)],
+                          "bans": bans})
+        ids, lps = self.runner.verify(vrows)
+        self.stats["decode_steps"] += 1
+        self.stats["spec_steps"] += 1
+        for r, d, s, lp in zip(self.running, drafts, ids, lps):
+            self.stats["spec_drafted"] += len(d)
+            for t in range(len(s)):
+                if t > 0 and s[t - 1] != d[t - 1]:
+                    break  # draft t was wrong: sample t was drawn after a token the request does not have
+                self._append(r, s[t], lp[t])
+                self.stats["decode_tokens"] += 1
+                self.stats["spec_accepted"] += t > 0
+                if r.done:
+                    self._finish(r)
+                    finished.append(r)
+                    break
+        return True
 
     def _drain(self, finished):
         """Read the in-flight decode step (before a synchronous runner call)."""

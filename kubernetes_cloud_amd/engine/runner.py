@@ -54,6 +54,21 @@ K / V of its own forward and quantizes only what it stores; chunked prefill sees
 earlier chunks dequantized (quantized values) and the current chunk exact. Composes with
 ``weight_dtype="fp8"``. Not covered: tensor-parallel and layer-split models, head dims
 outside D % 8 == 0, D <= 256, GQA groups other than 1 / 2 / 4 / 8 (``ValueError``).
+
+``spec_tokens=T`` (or ``KCA_DECODE_SPEC=T`` when the keyword is None; unset / ``0`` / ``none`` /
+``off``: off, the default; T in 2 / 4 / 8): speculative decoding. ``verify`` / ``verify_async`` run one
+step over up to T tokens per sequence -- its last token and up to T - 1 drafted ones -- as ``Bb * T``
+rows of the ordinary layer code (the matrix-core layer while the rows fit it, the per-projection path
+otherwise, so ``weight_dtype`` composes), with the attention on ``kca_spec_prep`` + ``kca_spec_attn``
+(``csrc/kernels/decode_spec.hip``): the T queries of a sequence share every K/V row load. Every row is
+sampled (its own seed and bans); the caller keeps the samples up to the first one that contradicts its
+draft (``LLMEngine``). Rejected positions stay in the cache past the sequence's length and the next step
+overwrites them. A bucket of T >= 4 whose KV stream is short (``KCA_DECODE_SPEC_ROWS_WORK``, default 65536
+(sequence, kv-head, position) rows; 0: never) runs ``kca_spec_prep`` + ``kca_decode_attn`` on the rows
+instead, where that measured faster (docs/PERF.md, Round 12). Each (batch, T, kv, sampler) bucket has its
+own static buffers and its own graph, apart from the decode graphs; ``spec_steps`` counts the steps built
+and ``step_launches[("spec", Bb, T)]`` their launches. Not covered (``ValueError``): T outside 2 / 4 / 8,
+(H / Hkv) * T > 8, tensor-parallel and layer-split models, ``kv_dtype="fp8"``.
 """
 from __future__ import annotations
 
@@ -68,6 +83,7 @@ from ..ops import _lib
 from ..ops import skinny_mm as smm
 from ..ops.gemv import embed_ln_rows, ln_rows, ln_skinny_linear, skinny_linear
 from ..ops import kv8
+from ..ops import spec
 from ..ops.kv8 import quantize_rows
 from ..ops import mx4
 from ..ops.w8 import quantize_weight, w8_linear
@@ -379,10 +395,26 @@ class DecodeHandle:
         return self._res
 
 
+class VerifyHandle:
+    """A launched verify step; ``result()`` waits for it: (ids, logprobs), per row the samples of its
+    n tokens (``ModelRunner.verify``)."""
+
+    __slots__ = ("handle", "ns", "T")
+
+    def __init__(self, handle, ns, T):
+        self.handle, self.ns, self.T = handle, ns, T
+
+    def result(self):
+        ids, lps = self.handle.result()
+        T = self.T
+        return ([ids[i * T:i * T + k] for i, k in enumerate(self.ns)],
+                [lps[i * T:i * T + k] for i, k in enumerate(self.ns)])
+
+
 class ModelRunner:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None,
-                 weight_dtype: str | None = None, kv_dtype: str | None = None):
+                 weight_dtype: str | None = None, kv_dtype: str | None = None, spec_tokens: int | str | None = None):
         self.model = model.eval()
         cfg = model.cfg
         self.cfg = cfg
@@ -405,6 +437,13 @@ class ModelRunner:
         self.mx4_steps = 0  # ... on the MXFP4 weights
         self._kv8 = self._kv_dtype(kv_dtype) == "fp8"
         self.kv8_steps = 0  # decode steps built on the FP8 KV cache (eager runs and graph captures)
+        self.spec_tokens = self._spec_tokens(spec_tokens)  # T rows per sequence of a verify step (0: off)
+        self.spec_steps = 0  # verify steps built (eager runs and graph captures)
+        self._spec = None  # the per-sequence arrays of the verify step being built (_attn)
+        # a verify bucket of T >= 4 with at most this many (sequence, kv-head, position) cache rows runs its
+        # attention as Bb * T rows of the one-token kernel (_spec_rows); 0: the multi-token kernel always
+        self._spec_rows_work = int(os.environ.get("KCA_DECODE_SPEC_ROWS_WORK", "65536"))
+        self.spec_rows_steps = 0  # verify steps built on that arm
         self.cache = KVCache(cfg.n_layers, max_slots, self.Hkv, self.max_len, self.D, self.device, self.dtype,
                              page_size=page_size, n_pages=kv_pages, layer_devices=self.layer_devs,
                              kv_dtype="fp8" if self._kv8 else None)
@@ -531,6 +570,38 @@ class ModelRunner:
                              f"{self.H} query / {self.Hkv} KV heads (needs head_dim % 8 == 0, <= 256, and "
                              f"{kv8.GROUPS} query heads per KV head); serve this model with the 16-bit KV cache")
         return "fp8"
+
+    def _spec_tokens(self, spec_tokens) -> int:
+        """Speculative decoding (module docstring): T in {2, 4, 8} or 0, from the keyword or KCA_DECODE_SPEC."""
+        if spec_tokens is None:
+            spec_tokens = os.environ.get("KCA_DECODE_SPEC", "") or None
+        if spec_tokens is None or spec_tokens is False or str(spec_tokens).strip().lower() in ("0", "none", "off"):
+            return 0
+        opt = f"spec_tokens / KCA_DECODE_SPEC: {spec_tokens!r}"
+        try:
+            T = int(spec_tokens)
+        except (TypeError, ValueError):
+            raise ValueError(f"{opt} (supported: 2, 4, 8, or unset)") from None
+        if T not in (2, 4, 8) or isinstance(spec_tokens, float):
+            raise ValueError(f"{opt} (supported: 2, 4, 8, or unset)")
+        from ..parallel import tensor_parallel as tpm
+        tp_types = tuple(t for t in (getattr(tpm, n, None) for n in
+                                     ("RowParallelLinear", "ColumnParallelLinear", "ParallelLMHead")) if t)
+        if any(isinstance(mm, tp_types) for mm in self.model.modules()):
+            raise ValueError(f"{opt} does not cover tensor-parallel models; serve this model without speculation")
+        if self.multi_device:
+            raise ValueError(f"{opt} does not cover a layer-split placement; serve this model without speculation")
+        if self._kv8:
+            raise ValueError(f"{opt} does not cover kv_dtype='fp8' (KCA_DECODE_KV=fp8): the multi-token attention "
+                             "kernel reads the 16-bit KV cache")
+        G = self.H // max(self.Hkv, 1)
+        if G * T > 8:
+            raise ValueError(f"{opt} with {G} query heads per KV head: the verify attention holds at most 8 "
+                             f"queries per KV head (T <= {max(8 // G, 1)})")
+        if not spec.supported(self.D, self.H, self.Hkv, T):
+            raise ValueError(f"{opt} does not cover head_dim {self.D} with {self.H} query / {self.Hkv} KV heads "
+                             "(needs head_dim % 8 == 0, <= 256, and (H / Hkv) * T in 2 / 4 / 8)")
+        return T
 
     def _quantize_decode_weights(self, weight_dtype):
         """Weight-only decode (module docstring): ``({id(linear): W8Weight} | None, {id(linear):
@@ -701,6 +772,26 @@ class ModelRunner:
                 tbl, by_row = pages, by_row | 2
         return cos, sin, tbl, by_row
 
+    def _attn(self, qkv, at, kc, vc, cos, sin, pos, slots, kv_lens, max_kv, obuf, ws, tbl, by_row):
+        """A layer's RoPE + cache append + attention for the step being built: one token per row
+        (``decode_prep_attention``), or -- while a verify step is built -- T rows per sequence
+        (``spec_prep_attention``, whose per-sequence arrays ``verify_async`` left in ``_spec``)."""
+        cfg = self.cfg
+        if self._spec is not None:
+            base, n_tok, sl, kl, T, rows = self._spec
+            assert not by_row, "a verify step looks its angles and pages up on the device"
+            if rows is not None:  # a short KV stream: the rows as sequences of their own (_spec_rows)
+                spec.spec_prep(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved, cos, sin, base, n_tok,
+                               sl, T, kc, vc, tbl)
+                return dops.decode_attention(qkv, kc, vc, rows[0], rows[1], self.H, max_kv, at.scale, at.alibi,
+                                             out=obuf, ws=ws, block_table=tbl, window=at.window)
+            return spec.spec_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved, cos, sin,
+                                            base, n_tok, sl, T, kc, vc, kl, max_kv, at.scale, at.alibi, out=obuf,
+                                            ws=ws, block_table=tbl, window=at.window)
+        return dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
+                                          cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
+                                          out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+
     def _layers_decode_fused(self, tokens, pos, slots, kv_lens, max_kv, ws, obuf):
         """Batch-1 decode step, one queue, the residual + next LayerNorm in each layer's last projection
         (see _fused_ok for the three layer kinds). Returns None (nothing launched) when the fused kernels
@@ -853,9 +944,7 @@ class ModelRunner:
                 # TP rank: partial projections, each closed by all-reduce + bias + residual + row statistics
                 ar, y = self._tp_ar, fz["y"]
                 smm.launch([smm.job([part(x1, at.qkv.weight, ln1)], qkv.shape[1], qkv, at.qkv.bias)], B, dt)
-                o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
-                                               cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
-                                               out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+                o = self._attn(qkv, at, kc, vc, cos, sin, pos, slots, kv_lens, max_kv, obuf, ws, tbl, by_row)
                 smm.mm(o, at.out.weight, out=y, packed=pk(at.out.weight))
                 ar.res_stats(y, at.out.bias, hb, hb, st, blk.ln_2.eps)
                 smm.launch([smm.job([part(hb, mlp.fc_in.weight, (st, blk.ln_2.weight, blk.ln_2.bias))],
@@ -865,9 +954,7 @@ class ModelRunner:
                 continue
             if kind == "seq":
                 smm.launch([smm.job([part(x1, at.qkv.weight, ln1)], qkv.shape[1], qkv, at.qkv.bias)], B, dt)
-                o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
-                                               cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
-                                               out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+                o = self._attn(qkv, at, kc, vc, cos, sin, pos, slots, kv_lens, max_kv, obuf, ws, tbl, by_row)
                 smm.launch([smm.job([part(o, at.out.weight)], hb.shape[1], hb, at.out.bias, res=hb, stats=st,
                                     eps=blk.ln_2.eps)], B, dt)
                 smm.launch([smm.job([part(hb, mlp.fc_in.weight, (st, blk.ln_2.weight, blk.ln_2.bias))],
@@ -883,9 +970,7 @@ class ModelRunner:
                 ln2, x2 = ln1, x1
             smm.launch([smm.job([part(x1, at.qkv.weight, ln1)], qkv.shape[1], qkv, at.qkv.bias),
                         smm.job([part(x2, mlp.fc_in.weight, ln2)], g.shape[1], g, mlp.fc_in.bias, act)], B, dt)
-            o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
-                                           cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
-                                           out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+            o = self._attn(qkv, at, kc, vc, cos, sin, pos, slots, kv_lens, max_kv, obuf, ws, tbl, by_row)
             smm.launch([smm.job([part(o, at.out.weight), part(g, mlp.fc_out.weight)], hb.shape[1], hb,
                                 fz["bias"][li], res=hb, stats=st, eps=nln.eps)], B, dt)
         w, b, grp = self._head_weight()
@@ -981,9 +1066,7 @@ class ModelRunner:
                                            self.cache.v_scale[li], kv_lens, max_kv, at.scale, at.alibi,
                                            out=obuf, ws=ws, block_table=tbl, window=at.window)
             else:
-                o = dops.decode_prep_attention(qkv, self.H, self.Hkv, self.D, self.rot, cfg.rotary_interleaved,
-                                               cos, sin, pos, slots, kc, vc, kv_lens, max_kv, at.scale, at.alibi,
-                                               out=obuf, ws=ws, block_table=tbl, window=at.window, by_row=by_row)
+                o = self._attn(qkv, at, kc, vc, cos, sin, pos, slots, kv_lens, max_kv, obuf, ws, tbl, by_row)
             a = self._lin(at.out, o)
             if side_out is not None:  # join
                 cur.wait_stream(self._side)
@@ -1093,12 +1176,13 @@ class ModelRunner:
         return (pk.d("rcos") if "rcos" in f else None, pk.d("rsin") if "rsin" in f else None,
                 pk.d("pages").view(Bb, self.cache.blocks) if "pages" in f else None)
 
-    def _outbuf(self, Bb: int):
+    def _outbuf(self, Bb: int, key=None):
         """Sampled ids (int64) and log-probs (fp32) of a batch bucket in ONE device buffer shared by its
         kv-length buckets -- one D2H copy per step, and a chained token (decode_async) is read by the
         next step's embedding kernel from a fixed address whatever kv bucket that step lands in --
         with two pinned landing buffers (one per host pk buffer)."""
-        ob = self._outbufs.get(Bb)
+        key = Bb if key is None else key  # (a verify bucket keeps its own: key ("spec", rows))
+        ob = self._outbufs.get(key)
         if ob is None:
             pin = self.device.type == "cuda"
             dev = torch.empty(3 * Bb, device=self.device, dtype=torch.int32)
@@ -1110,7 +1194,7 @@ class ModelRunner:
             ob = {"out": dev, "ids": dev[:2 * Bb].view(torch.int64), "lps": dev[2 * Bb:].view(torch.float32),
                   "flip": [0], "out_h": hs, "ids_h": [h[:2 * Bb].view(torch.int64) for h in hs],
                   "lps_h": [h[2 * Bb:].view(torch.float32) for h in hs]}
-            self._outbufs[Bb] = ob
+            self._outbufs[key] = ob
         return ob
 
     def _step_body(self, st, Bb, Kb, mc=False):
@@ -1273,12 +1357,14 @@ class ModelRunner:
             ev = None
         return DecodeHandle(ids_h, lps_h, n, ev, st["ids"])
 
-    def _capture(self, st, Bb, Kb, mc=False):
+    def _capture(self, st, Bb, Kb, mc=False, body=None, key=None):
+        """Capture a step into a graph: the decode step, or ``body`` (the verify step) under ``key``."""
+        body = body or self._step_body
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up (allocator, hipBLASLt heuristics)
-                self._step_body(st, Bb, Kb, mc)
+                body(st, Bb, Kb, mc)
         torch.cuda.current_stream().wait_stream(s)
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
@@ -1287,9 +1373,158 @@ class ModelRunner:
         # capture runs; under the default global mode that query fails ("operation not permitted when
         # stream is capturing") and the watchdog aborts the process
         with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-            self._step_body(st, Bb, Kb, mc)
-        self._graphs[(Bb, Kb, mc)] = g
+            body(st, Bb, Kb, mc)
+        self._graphs[key or (Bb, Kb, mc)] = g
         return g
+
+    # -------------------------------------------------------------- verify
+    def _spec_static_for(self, Bb: int, Kb: int):
+        """Static buffers of a verify bucket: Bb sequences x T rows, kv bucket Kb (apart from decode's)."""
+        T = self.spec_tokens
+        key = ("spec", Bb, T, Kb)
+        st = self._static.get(key)
+        if st is not None:
+            return st
+        M, NB = Bb * T, self.max_bans
+        pk = _Packed({"tokens": (torch.int64, M), "seeds": (torch.int64, M), "pos": (torch.int32, M),
+                      "base": (torch.int32, Bb), "n_tok": (torch.int32, Bb), "slots": (torch.int32, Bb),
+                      "kv_lens": (torch.int32, Bb), "row_slots": (torch.int32, M), "row_kv": (torch.int32, M),
+                      "seen_slots": (torch.int32, M), "top_k": (torch.int32, M), "temperature": (torch.float32, M),
+                      "top_p": (torch.float32, M), "rep": (torch.float32, M), "bans": (torch.int32, M * NB)},
+                     self.device)
+        ws_n = max(spec.spec_ws_floats(Bb, T, self.H, self.Hkv, self.D, Kb),
+                   dops.decode_ws_floats(M, self.H, self.Hkv, self.D, Kb))  # (either arm: _spec_rows)
+        st = {"pk": pk, "ws": torch.zeros(max(ws_n, 1), device=self.device, dtype=torch.float32),
+              "obuf": torch.empty(M, self.H * self.D, device=self.device, dtype=self.dtype),
+              "sws": torch.empty(M * self.V, device=self.device, dtype=torch.float32),
+              **self._outbuf(M, key=("spec", M))}
+        self._static[key] = st
+        return st
+
+    def _spec_rows(self, Bb: int, Kb: int) -> bool:
+        """Whether a verify bucket runs its attention as Bb * T rows of ``kca_decode_attn`` -- row (b, t) a
+        sequence of length pos + t + 1 -- after ``kca_spec_prep``, instead of ``kca_spec_attn``. The
+        multi-token kernel reads each K/V row once for T queries but has 1/T of the workgroups and T times
+        the arithmetic per workgroup; on a short KV stream that chain is longer than streaming the rows T
+        times (docs/PERF.md, Round 12: it loses at T >= 4 up to 65536 (sequence, kv-head, position) rows
+        and wins from 114688 on). bf16 only: ``kca_decode_attn`` has no fp16 twin."""
+        return (self.spec_tokens >= 4 and self.dtype == torch.bfloat16 and self.device.type == "cuda"
+                and Bb * self.Hkv * Kb <= self._spec_rows_work)
+
+    def _spec_step_body(self, st, Bb, Kb, mc=False):
+        """One verify step: the layer code on Bb * T rows with the attention switched to the multi-token
+        kernels (_attn), then the sampler on every row. The sampler's repetition mask: a row that may be
+        rejected must not mark it, so every row points at the scratch slot's mask row except the single
+        row of a request with a repetition penalty (such a request is never given drafts)."""
+        pk, T = st["pk"], self.spec_tokens
+        n0 = _lib.LAUNCHES[0]
+        self.spec_steps += 1
+        self._chain_src, self._step_desc = None, None
+        rows = (pk.d("row_slots"), pk.d("row_kv")) if self._spec_rows(Bb, Kb) else None
+        self.spec_rows_steps += rows is not None
+        self._spec = (pk.d("base"), pk.d("n_tok"), pk.d("slots"), pk.d("kv_lens"), T, rows)
+        try:
+            logits = self._layers_decode(pk.d("tokens"), pk.d("pos"), pk.d("slots"), pk.d("kv_lens"), Kb,
+                                         st["ws"], st["obuf"])
+        finally:
+            self._spec = None
+        dops.sample_logits(logits, temperature=pk.d("temperature"), top_k=pk.d("top_k"), top_p=pk.d("top_p"),
+                           rep_penalty=pk.d("rep"), seen=self.seen, slots=pk.d("seen_slots"),
+                           ban_ids=pk.d("bans").view(Bb * T, self.max_bans), seeds=pk.d("seeds"), step=0,
+                           ws=st["sws"], out_ids=st["ids"], out_logprobs=st["lps"], mwg_complete=mc)
+        self.step_launches[("spec", Bb, T)] = _lib.LAUNCHES[0] - n0
+
+    @torch.no_grad()
+    def verify(self, rows: list[dict]):
+        """rows: [{tokens: [t0, d1, .., d_{n-1}], pos, slot, temperature, top_k, top_p, rep, seeds: [n],
+        bans: [n lists]}], 1 <= n <= ``spec_tokens``: ``t0`` is the sequence's last token (position ``pos``,
+        its K/V not yet cached, as in ``decode``), ``d_i`` the drafted tokens after it. -> (ids, logprobs):
+        per row the n tokens sampled after ``t0``, after ``t0 d1``, ... and their log-probs. Sample t is
+        valid only if the drafts before it were right (d_i == sample i-1): the caller stops at the first
+        mismatch; the rejected rows' K/V stay past the sequence's length until overwritten."""
+        return self.verify_async(rows).result()
+
+    @torch.no_grad()
+    def verify_async(self, rows: list[dict]) -> "VerifyHandle":
+        """Launch one verify step without waiting for it (inputs in one packed H2D copy, outputs in one
+        D2H copy behind an event, as ``decode_async``)."""
+        T = self.spec_tokens
+        if not T:
+            raise RuntimeError("verify needs spec_tokens (KCA_DECODE_SPEC) set on the runner")
+        n = len(rows)
+        ns = [len(r["tokens"]) for r in rows]
+        if not all(1 <= k <= T for k in ns):
+            raise ValueError(f"a verify row takes 1..{T} tokens, got {ns}")
+        if any(r["pos"] + k > self.max_len for r, k in zip(rows, ns)):
+            raise ValueError("a verify row would write past max_len")
+        Bb = _next_pow2(n) if self.device.type == "cuda" else n
+        max_kv = max(r["pos"] + k for r, k in zip(rows, ns))
+        Kb = min(_next_pow2(max_kv, 256), self.max_len)
+        st = self._spec_static_for(Bb, Kb)
+        pk = st["pk"]
+        pk.flip()
+        NB, M = self.max_bans, Bb * T
+        for r, k in zip(rows, ns):
+            self.cache.reserve(r["slot"], r["pos"] + k)
+        self.cache.sync()
+        a = pk.np
+        a["bans"].fill(-1)
+        a["tokens"].fill(0)
+        a["seeds"].fill(0)
+        a["temperature"].fill(0.0)
+        a["top_k"].fill(0)
+        a["top_p"].fill(1.0)
+        a["rep"].fill(1.0)
+        scratch = self.cache.scratch
+        a["seen_slots"].fill(scratch)
+        a["pos"].fill(0)  # (a padding row: token 0 at position 0 to every kernel but the attention, which skips it
+        a["row_slots"].fill(scratch)  # -- or, on the rows arm, reads one row of the scratch slot)
+        a["row_kv"].fill(1)
+        for i in range(Bb):
+            if i >= n:  # padding sequence -> scratch slot
+                a["base"][i], a["n_tok"][i], a["slots"][i], a["kv_lens"][i] = 0, 1, scratch, 1
+                continue
+            r, k = rows[i], ns[i]
+            a["base"][i], a["n_tok"][i], a["slots"][i], a["kv_lens"][i] = r["pos"], k, r["slot"], r["pos"] + k
+            rp = float(r.get("rep", 1.0) or 1.0)
+            if rp != 1.0 and k != 1:
+                raise ValueError("a request with a repetition penalty verifies one token at a time")
+            if len(r["seeds"]) != k or len(r.get("bans") or [()] * k) != k:
+                raise ValueError("a verify row needs one seed and one ban list per token")
+            for t in range(k):
+                j = i * T + t
+                a["tokens"][j], a["pos"][j], a["seeds"][j] = r["tokens"][t], r["pos"] + t, r["seeds"][t]
+                a["row_slots"][j], a["row_kv"][j] = r["slot"], r["pos"] + t + 1
+                a["temperature"][j], a["top_k"][j], a["top_p"][j] = r["temperature"], r["top_k"], r["top_p"]
+                b = (r.get("bans") or [()] * k)[t] or ()
+                if len(b) > NB:
+                    raise ValueError(f"{len(b)} banned ids > max_bans={NB}")
+                for jj, tok in enumerate(b):
+                    a["bans"][j * NB + jj] = tok
+            if rp != 1.0:
+                a["rep"][i * T], a["seen_slots"][i * T] = rp, r["slot"]
+        te, tk = a["temperature"], a["top_k"]
+        mc = bool(((~(te[:M] > 0)) | ((tk[:M] >= 1) & (tk[:M] <= dops.MWG_KMAX))).all())
+        pk.upload()
+        if self.use_graphs:
+            gk = ("spec", Bb, T, Kb, mc)
+            g = self._graphs.get(gk)
+            if g is None:
+                g = self._capture(st, Bb, Kb, mc, body=self._spec_step_body, key=gk)
+            g.replay()
+        else:
+            self._spec_step_body(st, Bb, Kb, mc)
+        fl = st["flip"]
+        fl[0] ^= 1
+        k = fl[0]
+        if self.device.type == "cuda":
+            st["out_h"][k].copy_(st["out"], non_blocking=True)  # ids + log-probs, one copy
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            st["out_h"][k].copy_(st["out"])
+            ev = None
+        return VerifyHandle(DecodeHandle(st["ids_h"][k], st["lps_h"][k], M, ev, st["ids"]), ns, T)
 
     @torch.no_grad()
     def sample_first(self, logits: torch.Tensor, rows: list[dict]):
@@ -1319,4 +1554,4 @@ def mix_seed(seed: int, step: int) -> int:
     return x - (1 << 64) if x >= (1 << 63) else x
 
 
-__all__ = ["KVCache", "KVCacheFull", "ModelRunner", "DecodeHandle", "mix_seed", "math"]
+__all__ = ["KVCache", "KVCacheFull", "ModelRunner", "DecodeHandle", "VerifyHandle", "mix_seed", "math"]
