@@ -38,7 +38,12 @@ seed and the bans of its position, so greedy and seeded sampled outputs are what
 speculation. Drafts never reach past the request's ``max_new_tokens`` / ``max_len``, so the admission's
 page count stays exact. A request with a repetition penalty or a multi-token bad word, or without a
 proposal, rides along with one token; a step in which nobody has a draft is an ordinary decode step.
-The one-step lookahead is off while speculation is on. ``start()`` runs
+The one-step lookahead is off while speculation is on.
+Quantized-weight prefill (``prefill_weights="quantized"``, or ``KCA_PREFILL_WEIGHTS=quantized`` in the
+environment; off by default; needs ``weight_dtype``): prefill runs on the quantized weights as decode does and
+the runner releases the 16-bit weights of the quantized projections (engine/runner.py) -- one model per
+request, and the memory the quantization was for. Composes with ``kv_dtype="fp8"`` and ``spec_tokens``.
+``start()`` runs
 the loop on a background thread for the HTTP servers; ``generate()`` is the
 synchronous batch API used by the finetuner sampler and the evaluator.
 """
@@ -103,12 +108,14 @@ class LLMEngine:
                  max_prefill_tokens: int = 16384, runner=None, page_size: int | None = None,
                  kv_pages: int | None = None, prefill_chunk: int | None = None, pipeline: bool | None = None,
                  weight_dtype: str | None = None, kv_dtype: str | None = None,
-                 spec_tokens: int | str | None = None, proposer=None):
+                 spec_tokens: int | str | None = None, proposer=None, prefill_weights: str | None = None):
         # ``spec_tokens=T`` (2 / 4 / 8): speculative decoding (module docstring; None reads KCA_DECODE_SPEC);
         # ``proposer``: an object with ``propose(tokens, k) -> list[int]`` (default: engine.spec.NgramProposer)
         # ``weight_dtype="fp8"`` / ``"mxfp4"``: FP8 / MXFP4 weight-only decode (engine/runner.py; None reads
         # KCA_DECODE_WEIGHTS)
         # ``kv_dtype="fp8"``: FP8 KV cache (engine/runner.py; None reads KCA_DECODE_KV)
+        # ``prefill_weights="quantized"``: prefill on the quantized weights, 16-bit projection weights released
+        # (engine/runner.py; None reads KCA_PREFILL_WEIGHTS)
         # ``runner``: e.g. a tp_driver.CollectiveRunner that mirrors every call to TP follower ranks
         if runner is not None and weight_dtype is not None:
             raise ValueError("weight_dtype applies to the runner the engine builds; a supplied runner sets its own")
@@ -116,9 +123,12 @@ class LLMEngine:
             raise ValueError("kv_dtype applies to the runner the engine builds; a supplied runner sets its own")
         if runner is not None and spec_tokens is not None:
             raise ValueError("spec_tokens applies to the runner the engine builds; a supplied runner sets its own")
+        if runner is not None and prefill_weights is not None:
+            raise ValueError("prefill_weights applies to the runner the engine builds; a supplied runner sets its own")
         self.runner = runner or ModelRunner(model, max_slots=max_slots, max_len=max_len, use_graphs=use_graphs,
                                             page_size=page_size, kv_pages=kv_pages, weight_dtype=weight_dtype,
-                                            kv_dtype=kv_dtype, spec_tokens=spec_tokens)
+                                            kv_dtype=kv_dtype, spec_tokens=spec_tokens,
+                                            prefill_weights=prefill_weights)
         self.spec_tokens = int(getattr(self.runner, "spec_tokens", 0) or 0)
         if self.spec_tokens and pipeline:
             raise ValueError("pipeline=True (one-step lookahead) does not combine with speculative decoding")

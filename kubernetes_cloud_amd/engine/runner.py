@@ -32,7 +32,8 @@ decode step takes the per-projection path with those four projections on
 ``ln_rows`` + ``kca_w8_gemm``, streaming half the weight bytes. The LM head and
 the embeddings stay 16-bit. Prefill keeps using the 16-bit weights, so both copies
 stay resident: decode-time weight memory is 1.5x the 16-bit weights (2x with the
-default packed twins of the matrix-core layer, which this mode does not build).
+default packed twins of the matrix-core layer, which this mode does not build) --
+unless ``prefill_weights="quantized"`` (below) releases them.
 
 ``weight_dtype="mxfp4"`` (``KCA_DECODE_WEIGHTS=mxfp4``): MXFP4 weight-only decode, the same
 scheme one format further. The four projections of every block are quantized once
@@ -69,6 +70,21 @@ instead, where that measured faster (docs/PERF.md, Round 12). Each (batch, T, kv
 own static buffers and its own graph, apart from the decode graphs; ``spec_steps`` counts the steps built
 and ``step_launches[("spec", Bb, T)]`` their launches. Not covered (``ValueError``): T outside 2 / 4 / 8,
 (H / Hkv) * T > 8, tensor-parallel and layer-split models, ``kv_dtype="fp8"``.
+
+``prefill_weights="quantized"`` (or ``KCA_PREFILL_WEIGHTS=quantized`` when the keyword is None; unset / ``0`` /
+``16bit`` / ``off``: off, the default; needs ``weight_dtype`` "fp8" or "mxfp4", ``ValueError`` otherwise, and
+inherits that option's exclusions): prefill on the quantized weights too. ``prefill`` -- chunked prefill with
+``start`` included -- runs the four projections of every block through ``ops.wq_gemm.wq_linear``
+(``kca_wq_gemm``, csrc/kernels/gemm_wq.hip: one tiled matrix-core launch per projection, the MLP's
+activation fused into fc_in's); LayerNorms, RoPE, cache writes, flash attention, the final LayerNorm and
+the 16-bit LM head are as without the option, and so are decode and verify, which already run on the
+quantized weights. A request then sees ONE model, and the 16-bit weights of the projections are released as
+each is quantized: the parameter keeps its dtype and device with ``numel() == 0`` (the runner records its
+shape), and calling the module directly raises a ``RuntimeError``. A projection ``weight`` may live on the
+host when the runner is built (biases and everything else on the device): it is copied to the device one
+projection at a time, quantized there and dropped, so peak device memory is the quantized model plus one
+16-bit projection. ``weight_bytes()`` reports quantized / released / resident bytes and
+``wq_prefill_steps`` counts the projection calls. Composes with ``kv_dtype="fp8"`` and ``spec_tokens``.
 """
 from __future__ import annotations
 
@@ -87,6 +103,7 @@ from ..ops import spec
 from ..ops.kv8 import quantize_rows
 from ..ops import mx4
 from ..ops.w8 import quantize_weight, w8_linear
+from ..ops.wq_gemm import wq_linear
 
 # decode steps: each row's RoPE angles and page-table row travel with the step's packed inputs (fixed
 # device addresses), so every layer's attention chain loads them in its first memory round trip
@@ -414,7 +431,8 @@ class VerifyHandle:
 class ModelRunner:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None,
-                 weight_dtype: str | None = None, kv_dtype: str | None = None, spec_tokens: int | str | None = None):
+                 weight_dtype: str | None = None, kv_dtype: str | None = None, spec_tokens: int | str | None = None,
+                 prefill_weights: str | None = None):
         self.model = model.eval()
         cfg = model.cfg
         self.cfg = cfg
@@ -432,6 +450,9 @@ class ModelRunner:
         self.layer_devs = [blk.ln_1.weight.device for blk in model.h]
         self.head_dev = model.ln_f.weight.device
         self.multi_device = len({str(d) for d in self.layer_devs + [self.device, self.head_dev]}) > 1
+        self._wq_prefill = self._prefill_weights(prefill_weights)  # prefill on the quantized weights (module docstring)
+        self.released: dict = {}  # id(linear) -> the shape of its released 16-bit weight
+        self.wq_prefill_steps = 0  # prefill projections run on the quantized weights
         self._w8, self._mx4 = self._quantize_decode_weights(weight_dtype)
         self.w8_steps = 0  # decode steps built on the FP8 weights (eager runs and graph captures)
         self.mx4_steps = 0  # ... on the MXFP4 weights
@@ -610,6 +631,9 @@ class ModelRunner:
         if weight_dtype is None:
             weight_dtype = os.environ.get("KCA_DECODE_WEIGHTS", "") or None
         if weight_dtype in (None, "0", "none", "off"):
+            if self._wq_prefill:
+                raise ValueError("prefill_weights='quantized' (KCA_PREFILL_WEIGHTS=quantized) needs weight_dtype "
+                                 "'fp8' or 'mxfp4' (KCA_DECODE_WEIGHTS): there are no quantized weights to prefill on")
             return None, None
         if weight_dtype not in ("fp8", "mxfp4"):
             raise ValueError(f"weight_dtype / KCA_DECODE_WEIGHTS: {weight_dtype!r} "
@@ -625,14 +649,72 @@ class ModelRunner:
             raise ValueError(f"{opt} does not cover a layer-split placement; "
                              "serve this model with 16-bit weights")
         mods = [mod for blk in self.model.h for mod in (blk.attn.qkv, blk.attn.out, blk.mlp.fc_in, blk.mlp.fc_out)]
-        if weight_dtype == "fp8":
-            return {id(mod): quantize_weight(mod.weight) for mod in mods}, None
-        for mod in mods:
-            if mod.weight.shape[1] % mx4.BLOCK:
-                raise ValueError(f"{opt} does not cover a projection with K = {mod.weight.shape[1]} "
-                                 f"(MXFP4 blocks are {mx4.BLOCK} wide: K % {mx4.BLOCK} == 0); "
-                                 "serve this model with 16-bit weights")
-        return None, {id(mod): mx4.quantize_weight(mod.weight) for mod in mods}
+        if weight_dtype == "mxfp4":
+            for mod in mods:
+                if mod.weight.shape[1] % mx4.BLOCK:
+                    raise ValueError(f"{opt} does not cover a projection with K = {mod.weight.shape[1]} "
+                                     f"(MXFP4 blocks are {mx4.BLOCK} wide: K % {mx4.BLOCK} == 0); "
+                                     "serve this model with 16-bit weights")
+        quant = quantize_weight if weight_dtype == "fp8" else mx4.quantize_weight
+        if not self._wq_prefill:
+            qs = {id(mod): quant(mod.weight) for mod in mods}
+        else:  # one projection at a time: to the device if it lives on the host, quantized, released
+            qs = {}
+            for mod in mods:
+                qs[id(mod)] = quant(mod.weight.detach().to(self.device))
+                self._release(mod)
+        return (qs, None) if weight_dtype == "fp8" else (None, qs)
+
+    def _prefill_weights(self, prefill_weights) -> bool:
+        """``prefill_weights`` (module docstring): True for "quantized", from the keyword or
+        KCA_PREFILL_WEIGHTS."""
+        if prefill_weights is None:
+            prefill_weights = os.environ.get("KCA_PREFILL_WEIGHTS", "") or None
+        if prefill_weights in (None, "0", "16bit", "off"):
+            return False
+        if prefill_weights != "quantized":
+            raise ValueError(f"prefill_weights / KCA_PREFILL_WEIGHTS: {prefill_weights!r} "
+                             "(supported: 'quantized', '16bit', or unset)")
+        return True
+
+    def _release(self, mod):
+        """Drop a quantized projection's 16-bit weight: the parameter stays, with its dtype and device and
+        no elements; its shape goes to ``released``; calling the module raises."""
+        w = mod.weight
+        self.released[id(mod)] = (tuple(w.shape), w.element_size())
+        w.data = torch.empty(0, dtype=w.dtype, device=w.device)
+        if getattr(mod, "weight_t", None) is not None:
+            mod.weight_t = None
+
+        def refuse(module, args):
+            raise RuntimeError(f"{type(module).__name__}{self.released[id(module)][0]}: its 16-bit weight was released "
+                               "by prefill_weights=\"quantized\" (the runner prefills and decodes on the quantized "
+                               "weights); call the runner, not the module")
+
+        mod.register_forward_pre_hook(refuse)
+
+    def weight_bytes(self) -> dict:
+        """Bytes of the quantized projections, of the 16-bit weights released for them, and of every
+        parameter the model still holds."""
+        qs = self._w8 if self._w8 is not None else (self._mx4 or {})
+        return {"quantized": sum(q.nbytes() for q in qs.values()),
+                "released_16bit": sum(math.prod(shape) * es for shape, es in self.released.values()),
+                "resident_16bit": sum(p_.numel() * p_.element_size() for p_ in self.model.parameters())}
+
+    def _plin(self, mod, x, act: int = 0):
+        """A prefill projection: the module, or -- ``prefill_weights="quantized"`` -- ``wq_linear`` on its
+        quantized weight with the activation fused."""
+        if not self._wq_prefill:
+            return mod(x)
+        w = (self._w8 if self._w8 is not None else self._mx4)[id(mod)]
+        self.wq_prefill_steps += 1
+        return wq_linear(x.reshape(-1, x.shape[-1]), w, mod.bias, act).view(*x.shape[:-1], -1)
+
+    def _pmlp(self, mlp, x):
+        if not self._wq_prefill:
+            return mlp(x)
+        act = 1 if mlp.approx in ("tanh", True) else 2
+        return self._plin(mlp.fc_out, self._plin(mlp.fc_in, x, act))
 
     # ------------------------------------------------------------- prefill
     @torch.no_grad()
@@ -684,7 +766,7 @@ class ModelRunner:
                 h, pending = self._hop(self.layer_devs[li], h, pending)
             x, h = blk.ln_1(h, residual=pending) if pending else (blk.ln_1(h), h)
             at = blk.attn
-            qkv = at.qkv(x).view(n, T, 3, self.H, self.D)
+            qkv = self._plin(at.qkv, x).view(n, T, 3, self.H, self.D)
             q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
             if self.rot > 0:
                 ops.apply_rotary_(q, k, self.rot, T, cfg.rotary_interleaved, cfg.rotary_base,
@@ -694,13 +776,13 @@ class ModelRunner:
                 o = self._continued_attention(li, q, slots, lens, start, at, cur=(k, v))
             else:  # (GPT-Neo local layers: banded, the kernels skip the tiles left of the band)
                 o = ops.flash_attention(q, k, v, causal=True, scale=at.scale, alibi=at.alibi, window=at.window)
-            a = at.out(o.reshape(n, T, -1))
+            a = self._plin(at.out, o.reshape(n, T, -1))
             if cfg.parallel_residual:
                 x2 = x if blk.ln_2 is None else blk.ln_2(h)
-                pending = (a, blk.mlp(x2))
+                pending = (a, self._pmlp(blk.mlp, x2))
             else:
                 x2, h = blk.ln_2(h, residual=(a,))
-                pending = (blk.mlp(x2),)
+                pending = (self._pmlp(blk.mlp, x2),)
         if self.multi_device and h.device != self.head_dev:
             h, pending = self._hop(self.head_dev, h, pending)
         if ragged:

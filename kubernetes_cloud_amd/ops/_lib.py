@@ -99,6 +99,9 @@ _SIGS = {
     "kca_w8_set_kgroups": [I],
     # MXFP4 weights (csrc/kernels/gemv_mx4.hip): kca_w8_gemm's arguments with e2m1 nibbles and e8m0 block scales
     "kca_mx4_gemm": [P, LL, P, P, P, P, LL, I, I, I, I, I, P],
+    # quantized-weight prefill GEMM (csrc/kernels/gemm_wq.hip): the same arguments, any M; the int before
+    # the stream is fmt (0 FP8 as kca_w8_gemm, 1 MXFP4 as kca_mx4_gemm)
+    "kca_wq_gemm": [P, LL, P, P, P, P, LL, I, I, I, I, I, I, P],
     # FP8 KV cache (csrc/kernels/decode_kv8.hip); the last int before the stream is dt (0 bf16, 1 fp16)
     "kca_kv8_prep": [P, LL, I, I, I, I, I, I, P, P, P, P, P, P, P, P, LL, LL, LL, LL, LL, P, I, I, I, P],
     "kca_kv8_attn": [P, LL, P, P, P, P, LL, LL, LL, LL, LL, P, P, P, LL, P, LL, I, I, I, I, I, I, F, P, P, I, I, I,
