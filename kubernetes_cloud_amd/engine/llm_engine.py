@@ -43,6 +43,20 @@ Quantized-weight prefill (``prefill_weights="quantized"``, or ``KCA_PREFILL_WEIG
 environment; off by default; needs ``weight_dtype``): prefill runs on the quantized weights as decode does and
 the runner releases the 16-bit weights of the quantized projections (engine/runner.py) -- one model per
 request, and the memory the quantization was for. Composes with ``kv_dtype="fp8"`` and ``spec_tokens``.
+Prefix caching (``prefix_cache=True``, or ``KCA_PREFIX_CACHE=1`` in the environment; off by default; paged
+cache only): requests share the KV pages of a common prompt prefix -- a system prompt, a few-shot block,
+the earlier turns of a chat. A page is registered in the cache's index (``KVCache``) once prefill has
+written all of its positions (per chunk under ``prefill_chunk``), and when a request finishes the pages
+lying wholly below ``len(prompt) + len(output) - 1`` follow (the last sampled token's K/V may never have
+been written), so the next turn of a conversation hits. Admission takes the longest registered chain of
+full pages of the prompt, at most ``(len(prompt) - 1) // PS`` pages -- at least one token is computed, for
+its logits -- adopts it (``ModelRunner.adopt_prefix``) and prefills only the rest; hits and misses batch
+together, grouped by the length still to compute. Admission control is unchanged: every request commits
+its worst case in full, so the pages in use never exceed the commitment and free plus evictable pages
+always cover it; index pages nobody uses are evicted, least recently used first, when the free list runs
+short. ``beam_generate`` neither looks up nor registers. ``stats``: ``prefix_lookups``,
+``prefix_hit_tokens``, ``prefix_registered_pages``, ``prefix_evictions``; ``prefill_tokens`` counts computed
+tokens only.
 ``start()`` runs
 the loop on a background thread for the HTTP servers; ``generate()`` is the
 synchronous batch API used by the finetuner sampler and the evaluator.
@@ -108,7 +122,8 @@ class LLMEngine:
                  max_prefill_tokens: int = 16384, runner=None, page_size: int | None = None,
                  kv_pages: int | None = None, prefill_chunk: int | None = None, pipeline: bool | None = None,
                  weight_dtype: str | None = None, kv_dtype: str | None = None,
-                 spec_tokens: int | str | None = None, proposer=None, prefill_weights: str | None = None):
+                 spec_tokens: int | str | None = None, proposer=None, prefill_weights: str | None = None,
+                 prefix_cache: bool | str | None = None):
         # ``spec_tokens=T`` (2 / 4 / 8): speculative decoding (module docstring; None reads KCA_DECODE_SPEC);
         # ``proposer``: an object with ``propose(tokens, k) -> list[int]`` (default: engine.spec.NgramProposer)
         # ``weight_dtype="fp8"`` / ``"mxfp4"``: FP8 / MXFP4 weight-only decode (engine/runner.py; None reads
@@ -116,6 +131,8 @@ class LLMEngine:
         # ``kv_dtype="fp8"``: FP8 KV cache (engine/runner.py; None reads KCA_DECODE_KV)
         # ``prefill_weights="quantized"``: prefill on the quantized weights, 16-bit projection weights released
         # (engine/runner.py; None reads KCA_PREFILL_WEIGHTS)
+        # ``prefix_cache=True``: requests share the KV pages of a common prompt prefix (module docstring; None
+        # reads KCA_PREFIX_CACHE)
         # ``runner``: e.g. a tp_driver.CollectiveRunner that mirrors every call to TP follower ranks
         if runner is not None and weight_dtype is not None:
             raise ValueError("weight_dtype applies to the runner the engine builds; a supplied runner sets its own")
@@ -125,10 +142,12 @@ class LLMEngine:
             raise ValueError("spec_tokens applies to the runner the engine builds; a supplied runner sets its own")
         if runner is not None and prefill_weights is not None:
             raise ValueError("prefill_weights applies to the runner the engine builds; a supplied runner sets its own")
+        if runner is not None and prefix_cache is not None:
+            raise ValueError("prefix_cache applies to the runner the engine builds; a supplied runner sets its own")
         self.runner = runner or ModelRunner(model, max_slots=max_slots, max_len=max_len, use_graphs=use_graphs,
                                             page_size=page_size, kv_pages=kv_pages, weight_dtype=weight_dtype,
                                             kv_dtype=kv_dtype, spec_tokens=spec_tokens,
-                                            prefill_weights=prefill_weights)
+                                            prefill_weights=prefill_weights, prefix_cache=prefix_cache)
         self.spec_tokens = int(getattr(self.runner, "spec_tokens", 0) or 0)
         if self.spec_tokens and pipeline:
             raise ValueError("pipeline=True (one-step lookahead) does not combine with speculative decoding")
@@ -161,6 +180,11 @@ class LLMEngine:
                       "prefill_pad_tokens": 0, "prefill_chunks": 0, "max_step_prefill_tokens": 0,
                       "decode_steps": 0, "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         cache = getattr(self.runner, "cache", None)
+        # prefix caching (module docstring): only with a runner of this process (a CollectiveRunner's
+        # followers keep caches of their own)
+        self.prefix_cache = isinstance(self.runner, ModelRunner) and bool(self.runner.prefix_cache)
+        if self.prefix_cache:
+            self.stats.update(prefix_lookups=0, prefix_hit_tokens=0, prefix_registered_pages=0, prefix_evictions=0)
         self._paged = cache is not None and getattr(cache, "paged", False)
         self._page_budget = cache.n_pages if self._paged else 0
         self._committed = 0  # worst-case pages promised to admitted requests
@@ -245,8 +269,26 @@ class LLMEngine:
             r.slot = -1
             self._committed -= self._pages_needed(r)
 
+    def _register(self, r: Request, n_tokens: int):
+        """Prefix caching: the pages of ``r`` lying wholly below position ``n_tokens`` into the index."""
+        if self.prefix_cache and r.slot >= 0:
+            cache = self.runner.cache
+            cache.register(r.slot, r.tokens, n_tokens // cache.page_size)
+            self.stats["prefix_registered_pages"] = cache.prefix_registered
+
+    def _lookup(self, r: Request):
+        """Prefix caching: adopt the longest cached chain of full pages of ``r``'s prompt into its slot."""
+        cache = self.runner.cache
+        pages = cache.lookup(r.prompt, (len(r.prompt) - 1) // cache.page_size)
+        self.stats["prefix_lookups"] += 1
+        if pages:
+            r.prefilled = len(pages) * cache.page_size
+            self.runner.adopt_prefix(r.slot, pages, r.prompt[:r.prefilled])
+            self.stats["prefix_hit_tokens"] += r.prefilled
+
     def _finish(self, r: Request):
         r.t_done = time.perf_counter()
+        self._register(r, len(r.tokens) - 1)  # (the last sampled token's K/V may never have been written)
         self._free_slot(r)
         self.stats["finished"] += 1
         if r.future is not None and not r.future.done():
@@ -307,6 +349,7 @@ class LLMEngine:
             ids = torch.tensor([r.prompt[p0:p0 + n]], dtype=torch.long)
             logits = self.runner.prefill(ids, [r.slot], [n], start=[p0])
             r.prefilled += n
+            self._register(r, r.prefilled)
             used += n
             self.stats["prefill_tokens"] += n
             self.stats["prefill_chunks"] += 1
@@ -338,22 +381,32 @@ class LLMEngine:
                 r = self.waiting.pop(0)
                 r.slot = self.free.pop()
                 self._committed += need
-                if chunked and len(r.prompt) > budget:  # prefill this one chunk by chunk
-                    r.prefilled = 0
+                r.prefilled = 0
+                if self.prefix_cache:
+                    self._lookup(r)
+                if chunked and len(r.prompt) - r.prefilled > budget:  # prefill this one chunk by chunk
                     self.prefilling.append(r)
                     break
-                budget -= len(r.prompt)
+                budget -= len(r.prompt) - r.prefilled
                 admit.append(r)
         if self.prefilling and budget > 0 and chunked:
             used += self._chunk_step(budget, finished)
         for group in _prefill_groups(admit):
-            T = max(len(r.prompt) for r in group)
-            lens = [len(r.prompt) for r in group]
-            ids = torch.tensor([r.prompt + [0] * (T - len(r.prompt)) for r in group], dtype=torch.long)
-            if all(L == T for L in lens):
+            # (prefix caching: r.prefilled tokens of the prompt are adopted pages; the rest is computed)
+            start = [r.prefilled for r in group]
+            lens = [len(r.prompt) - r.prefilled for r in group]
+            T = max(lens)
+            ids = torch.tensor([r.prompt[r.prefilled:] + [0] * (T - L) for r, L in zip(group, lens)],
+                               dtype=torch.long)
+            if any(start):
+                logits = self.runner.prefill(ids, [r.slot for r in group], lens, start=start)
+            elif all(L == T for L in lens):
                 logits = self.runner.prefill(ids, [r.slot for r in group])
             else:
                 logits = self.runner.prefill(ids, [r.slot for r in group], lens)
+            for r in group:
+                r.prefilled = len(r.prompt)
+                self._register(r, r.prefilled)
             toks, lps = self.runner.sample_first(logits, [self._row(r, 0) for r in group])
             self.stats["prefill_tokens"] += sum(lens)
             used += sum(lens)
@@ -382,6 +435,8 @@ class LLMEngine:
                 self.stats["decode_steps"] += 1
                 self._take(self.running, toks, lps, finished)
             self.running = [r for r in self.running if not r.done]
+        if self.prefix_cache:
+            self.stats["prefix_evictions"] = self.runner.cache.prefix_evictions
         self.stats["steps"] += 1
         self.stats["max_step_prefill_tokens"] = max(self.stats["max_step_prefill_tokens"], used)
         return finished
@@ -546,10 +601,11 @@ class LLMEngine:
 def _prefill_groups(reqs: list[Request], slack: float = 0.25, min_slack: int = 256) -> list[list[Request]]:
     """Length-sorted batches whose right padding stays within ``slack`` of the
     real tokens (or ``min_slack`` tokens: short prompts are launch-bound, so
-    they batch freely)."""
+    they batch freely). The length is what prefill computes: the prompt less
+    the ``prefilled`` tokens a prefix-cache hit adopted."""
     out, cur, real = [], [], 0
-    for r in sorted(reqs, key=lambda r: len(r.prompt)):
-        L = len(r.prompt)
+    for r in sorted(reqs, key=lambda r: len(r.prompt) - r.prefilled):
+        L = len(r.prompt) - r.prefilled
         if cur and L * (len(cur) + 1) - (real + L) > max(slack * (real + L), min_slack):
             out.append(cur)
             cur, real = [], 0

@@ -85,6 +85,22 @@ host when the runner is built (biases and everything else on the device): it is 
 projection at a time, quantized there and dropped, so peak device memory is the quantized model plus one
 16-bit projection. ``weight_bytes()`` reports quantized / released / resident bytes and
 ``wq_prefill_steps`` counts the projection calls. Composes with ``kv_dtype="fp8"`` and ``spec_tokens``.
+
+``prefix_cache=True`` (or ``KCA_PREFIX_CACHE=1`` when the keyword is None; unset / ``0`` / ``off``: off, the
+default): prefix caching. The cache keeps an index of the full prompt pages it holds (``KVCache``) and
+``adopt_prefix`` installs a matched chain of them, shared, as the first pages of a slot; ``prefill`` then
+computes only the rest with ``start`` = the adopted length. With the option on, a continued prefill -- a
+prefix hit or a chunk of ``prefill_chunk``, anything with a ``start`` > 0 in the batch -- runs ONE
+``kca_prefill_paged_attn`` launch per layer for the whole ragged batch (``ops.prefill_paged``,
+csrc/kernels/prefill_paged.hip: the flash-attention forward with its K/V tiles read through the block
+table; bf16 and fp16) instead of gathering every row's keys into fresh tensors and attending row by row.
+Layers the kernel does not cover (``ops.prefill_paged.supported``: GPT-Neo's local layers) keep that gather
+loop, and so does the one shape at which it measured faster (``_paged_prefill``: a single bf16 row of
+>= 512 queries behind >= 2048 cached tokens). ``paged_prefill_calls`` / ``gather_prefill_calls`` count the layer calls of either kind. With the
+option off nothing changes. Composes with ``weight_dtype``, ``prefill_weights="quantized"``, ``spec_tokens``
+and ``prefill_chunk``. Not covered (``ValueError``): ``page_size=0``, tensor-parallel and layer-split models,
+and ``kv_dtype="fp8"`` -- a hit would see its prefix quantized where a miss sees it exact, so outputs would
+depend on what the cache happens to hold; the kernel reads 16-bit pages only.
 """
 from __future__ import annotations
 
@@ -100,6 +116,7 @@ from ..ops import skinny_mm as smm
 from ..ops.gemv import embed_ln_rows, ln_rows, ln_skinny_linear, skinny_linear
 from ..ops import kv8
 from ..ops import spec
+from ..ops import prefill_paged
 from ..ops.kv8 import quantize_rows
 from ..ops import mx4
 from ..ops.w8 import quantize_weight, w8_linear
@@ -143,6 +160,17 @@ class KVCache:
     ``v_scale`` (fp32, ``shape[:-1]``) one scale per (token, kv-head) row (``ops.kv8``): (D + 4) / 2D of
     the 16-bit cache's bytes. Pages, the block table, the scratch page / slot and ``fork`` work as above
     (scales travel with their rows). The default (None) is the 16-bit cache, with no scale tensors.
+
+    Prefix index (``enable_prefix_index``; paged caches, ``ModelRunner(prefix_cache=True)``): full pages of
+    prompts are registered under ``(parent page id or -1, the page's PS token ids)`` -- compared by value,
+    so no hash collision can serve another prompt's K/V -- and ``lookup`` returns the longest registered
+    chain of a prompt for ``adopt``. The index holds one reference per registered page; a page held by
+    nobody else is evictable and counts as free (``free_count``): ``reserve`` and ``fork`` evict in LRU
+    order (a use refreshes the whole chain; ties go deepest first, so a page never leaves before a page
+    that extends it) when the free list runs short, and raise ``KVCacheFull`` only after that. A slot
+    registers a page only under a parent it holds itself (registration stops at a key that another page
+    already serves), so whoever holds a registered page holds its ancestors: the pages with no holder but
+    the index are closed under "extends" and all of them can go.
     """
 
     def __init__(self, n_layers: int, slots: int, kv_heads: int, max_len: int, head_dim: int,
@@ -178,6 +206,7 @@ class KVCache:
             self.n_pages = 0
             shape = (slots + 1, kv_heads, max_len, head_dim)
             self.tables = {}
+        self._pidx = None  # prefix index: (parent page or -1, token tuple) -> page (enable_prefix_index)
         self.dtype = dtype  # the model's element type (an FP8 cache dequantizes to it for chunked prefill)
         if kv_dtype == "fp8":
             dtype = torch.uint8
@@ -205,7 +234,87 @@ class KVCache:
         return -(-n_tokens // self.page_size) if self.paged else 0
 
     def free_count(self) -> int:
-        return len(self.free_pages) if self.paged else 0
+        if not self.paged:
+            return 0
+        return len(self.free_pages) + (len(self._evictable()) if self._pidx is not None else 0)
+
+    # ---------------------------------------------------------- prefix index
+    def enable_prefix_index(self):
+        if not self.paged:
+            raise ValueError("the prefix index needs a paged cache (page_size > 0)")
+        self._pidx = {}
+        self._pinfo: dict = {}  # page -> [key, depth, last use]
+        self._ptick = 0
+        self.prefix_registered = 0  # pages ever registered
+        self.prefix_evictions = 0
+
+    def _evictable(self) -> list[int]:
+        """Registered pages nobody but the index holds (class docstring: all of them can go)."""
+        return [pg for pg in self._pinfo if self.ref[pg] == 1]
+
+    def _evict(self, n: int):
+        """Up to ``n`` index-only pages back to the free list, least recently used and deepest first."""
+        victims = sorted(self._evictable(), key=lambda pg: (self._pinfo[pg][2], -self._pinfo[pg][1]))[:n]
+        for pg in victims:
+            del self._pidx[self._pinfo.pop(pg)[0]]
+            self.prefix_evictions += 1
+        self._drop(victims)
+
+    def lookup(self, tokens: list, max_pages: int) -> list[int]:
+        """The longest registered chain of full pages of ``tokens`` (at most ``max_pages``), refreshed."""
+        PS, parent, chain = self.page_size, -1, []
+        for i in range(min(max_pages, len(tokens) // PS)):
+            pg = self._pidx.get((parent, tuple(tokens[i * PS:(i + 1) * PS])))
+            if pg is None:
+                break
+            chain.append(pg)
+            parent = pg
+        self._touch(chain)
+        return chain
+
+    def clear_prefix_index(self):
+        """Every page nobody but the index holds goes back to the free list."""
+        self._evict(len(self._pinfo))
+
+    def _touch(self, chain):
+        self._ptick += 1
+        for pg in chain:
+            self._pinfo[pg][2] = self._ptick
+
+    def register(self, slot: int, tokens: list, n_pages: int) -> int:
+        """Pages [0, n_pages) of ``slot`` -- full, holding ``tokens[:n_pages * PS]`` -- into the index.
+        A key that is present keeps its page; registration stops where that page is not the slot's own.
+        Returns the number of pages added."""
+        PS, parent, chain, added = self.page_size, -1, [], 0
+        own = self.pages[slot]
+        for i in range(min(n_pages, len(own), len(tokens) // PS)):
+            key = (parent, tuple(tokens[i * PS:(i + 1) * PS]))
+            pg = self._pidx.get(key)
+            if pg is None:
+                pg = own[i]
+                if pg in self._pinfo:  # already serves another key (its old parent was evicted)
+                    break
+                self._pidx[key] = pg
+                self._pinfo[pg] = [key, i, 0]
+                self.ref[pg] += 1
+                added += 1
+            elif pg != own[i]:
+                break
+            chain.append(pg)
+            parent = pg
+        self._touch(chain)
+        self.prefix_registered += added
+        return added
+
+    def adopt(self, slot: int, pages: list[int]):
+        """``pages`` (a ``lookup`` chain) become the first pages of the empty ``slot``, shared."""
+        assert self.paged and not self.pages[slot]
+        for pg in pages:
+            self.ref[pg] += 1
+        self.pages[slot] = list(pages)
+        if pages:
+            self.table_h[slot, :len(pages)] = torch.tensor(pages, dtype=torch.int32)
+            self._dirty = True
 
     # ------------------------------------------------------------ page table
     def reserve(self, slot: int, n_tokens: int):
@@ -216,6 +325,8 @@ class KVCache:
         need = self.pages_for(min(n_tokens, self.max_len)) - len(own)
         if need <= 0:
             return
+        if len(self.free_pages) < need <= self.free_count():  # (a request that cannot fit evicts nothing)
+            self._evict(need - len(self.free_pages))
         if need > len(self.free_pages):
             raise KVCacheFull(f"slot {slot} needs {need} KV pages, {len(self.free_pages)} free")
         for _ in range(need):
@@ -274,6 +385,8 @@ class KVCache:
                 self.ref[pg] += 1
             lst = list(shared)
             if part:
+                if not self.free_pages and self._pidx is not None:
+                    self._evict(1)
                 if not self.free_pages:
                     self._drop([pg for l_ in new_lists for pg in l_] + lst)
                     raise KVCacheFull("no free KV page for a beam fork")
@@ -432,7 +545,7 @@ class ModelRunner:
     def __init__(self, model, max_slots: int = 32, max_len: int | None = None, use_graphs: bool | None = None,
                  max_bans: int = 16, page_size: int | None = None, kv_pages: int | None = None,
                  weight_dtype: str | None = None, kv_dtype: str | None = None, spec_tokens: int | str | None = None,
-                 prefill_weights: str | None = None):
+                 prefill_weights: str | None = None, prefix_cache: bool | str | None = None):
         self.model = model.eval()
         cfg = model.cfg
         self.cfg = cfg
@@ -465,9 +578,14 @@ class ModelRunner:
         # attention as Bb * T rows of the one-token kernel (_spec_rows); 0: the multi-token kernel always
         self._spec_rows_work = int(os.environ.get("KCA_DECODE_SPEC_ROWS_WORK", "65536"))
         self.spec_rows_steps = 0  # verify steps built on that arm
+        self.prefix_cache = self._prefix_cache(prefix_cache, page_size)  # prefix caching (module docstring)
+        self.paged_prefill_calls = 0  # continued-prefill layer calls on kca_prefill_paged_attn
+        self.gather_prefill_calls = 0  # ... on the gather loop (_continued_attention)
         self.cache = KVCache(cfg.n_layers, max_slots, self.Hkv, self.max_len, self.D, self.device, self.dtype,
                              page_size=page_size, n_pages=kv_pages, layer_devices=self.layer_devs,
                              kv_dtype="fp8" if self._kv8 else None)
+        if self.prefix_cache:
+            self.cache.enable_prefix_index()
         self.max_slots = max_slots
         self.rot = cfg.rotary_dim
         self._rope = {}
@@ -624,6 +742,30 @@ class ModelRunner:
                              "(needs head_dim % 8 == 0, <= 256, and (H / Hkv) * T in 2 / 4 / 8)")
         return T
 
+    def _prefix_cache(self, prefix_cache, page_size: int) -> bool:
+        """Prefix caching (module docstring): from the keyword or KCA_PREFIX_CACHE."""
+        if prefix_cache is None:
+            prefix_cache = os.environ.get("KCA_PREFIX_CACHE", "") or None
+        if prefix_cache is None or prefix_cache is False or str(prefix_cache).strip().lower() in ("0", "none", "off"):
+            return False
+        if prefix_cache is not True and str(prefix_cache).strip().lower() not in ("1", "on", "true"):
+            raise ValueError(f"prefix_cache / KCA_PREFIX_CACHE: {prefix_cache!r} (supported: True / 1, or unset)")
+        opt = "prefix_cache=True (KCA_PREFIX_CACHE=1)"
+        if not page_size:
+            raise ValueError(f"{opt} needs the paged KV cache (page_size > 0): shared prefixes are shared pages")
+        from ..parallel import tensor_parallel as tpm
+        tp_types = tuple(t for t in (getattr(tpm, n, None) for n in
+                                     ("RowParallelLinear", "ColumnParallelLinear", "ParallelLMHead")) if t)
+        if any(isinstance(mm, tp_types) for mm in self.model.modules()):
+            raise ValueError(f"{opt} does not cover tensor-parallel models; serve this model without it")
+        if self.multi_device:
+            raise ValueError(f"{opt} does not cover a layer-split placement; serve this model without it")
+        if self._kv8:
+            raise ValueError(f"{opt} does not cover kv_dtype='fp8' (KCA_DECODE_KV=fp8): a hit would see its prefix "
+                             "quantized where a miss sees it exact, and the paged prefill kernel reads the 16-bit "
+                             "KV cache")
+        return True
+
     def _quantize_decode_weights(self, weight_dtype):
         """Weight-only decode (module docstring): ``({id(linear): W8Weight} | None, {id(linear):
         MX4Weight} | None)`` of every block's four projections -- FP8, MXFP4, or both None with the
@@ -761,6 +903,7 @@ class ModelRunner:
                        + torch.arange(T, device=self.device)[None]).clamp_(max=self.max_len - 1)
         h = m.embed(ids, pos_ids if cont else None)
         pending = ()
+        rows_d = None
         for li, blk in enumerate(m.h):
             if self.multi_device and h.device != self.layer_devs[li]:
                 h, pending = self._hop(self.layer_devs[li], h, pending)
@@ -772,7 +915,15 @@ class ModelRunner:
                 ops.apply_rotary_(q, k, self.rot, T, cfg.rotary_interleaved, cfg.rotary_base,
                                   pos_ids=pos_ids, max_pos=self.max_len)
             self.cache.write(li, k, v, slots, lens, plan, start)
-            if cont:
+            if cont and self.prefix_cache and self._paged_prefill(at, n, T, start):
+                if rows_d is None:  # one upload per prefill: the rows' slots, first positions and lengths
+                    rows_d = torch.tensor([slots, start, lens], dtype=torch.int32).to(self.device)
+                o = prefill_paged.prefill_paged_attention(q, self.cache.k[li], self.cache.v[li], rows_d[0], rows_d[1],
+                                                          rows_d[2], at.scale, at.alibi,
+                                                          block_table=self.cache.table_on(self.layer_devs[li]))
+                self.paged_prefill_calls += 1
+            elif cont:
+                self.gather_prefill_calls += 1
                 o = self._continued_attention(li, q, slots, lens, start, at, cur=(k, v))
             else:  # (GPT-Neo local layers: banded, the kernels skip the tiles left of the band)
                 o = ops.flash_attention(q, k, v, causal=True, scale=at.scale, alibi=at.alibi, window=at.window)
@@ -793,6 +944,18 @@ class ModelRunner:
             pick = lambda t: t[:, -1:]  # noqa: E731
         y, _ = m.ln_f(pick(h), residual=tuple(pick(p_) for p_ in pending))
         return m.logits_from_hidden(y)[:, -1].to(self.device)
+
+    def _paged_prefill(self, at, n: int, T: int, start: list[int]) -> bool:
+        """Whether a continued prefill's attention runs ``kca_prefill_paged_attn``: where the kernel covers
+        the layer, except ONE bf16 row of >= 512 queries behind >= 2048 cached tokens, the one cell of
+        bench/prefix_bench.py where the gather loop measured faster by more than the spread (NeoX heads:
+        0.149 against 0.159 ms; one row is 4 query tiles x H workgroups, and the gathered copy takes
+        flash attention's full-tile path; docs/PERF.md, Round 14). fp16 always runs the kernel: the gather
+        loop's flash attention is not native for it."""
+        if not prefill_paged.supported(self.D, self.H, self.Hkv, at.window):
+            return False
+        return not (n == 1 and T >= 512 and start[0] >= 2048 and self.dtype == torch.bfloat16
+                    and self.device.type == "cuda")
 
     def _continued_attention(self, li, q, slots, lens, start, at, cur=None):
         """Chunk queries [start, start + L) of each row against the slot's cached
@@ -1336,6 +1499,20 @@ class ModelRunner:
     def release(self, slot: int):
         """A finished sequence's KV pages go back to the pool."""
         self.cache.release(slot)
+
+    @torch.no_grad()
+    def adopt_prefix(self, slot: int, pages: list[int], tokens: list[int]):
+        """Prefix caching: ``pages`` (a ``KVCache.lookup`` chain holding the K/V of ``tokens``) become the
+        first pages of ``slot``, shared, and ``tokens`` its seen set -- the repetition penalty sees the
+        cached prefix. ``prefill(..., start=[len(tokens)])`` continues from there (it resets neither)."""
+        if not self.prefix_cache:
+            raise ValueError("adopt_prefix needs prefix_cache=True (KCA_PREFIX_CACHE=1)")
+        assert len(tokens) == len(pages) * self.cache.page_size
+        self.cache.release(slot)
+        self.cache.adopt(slot, pages)
+        self.seen[slot] = 0
+        if tokens:
+            self.seen[slot, torch.tensor(tokens, device=self.device, dtype=torch.long)] = 1
 
     pipelined = True  # supports decode_async (the TP CollectiveRunner does not)
 

@@ -109,6 +109,8 @@ _SIGS = {
     # speculative decoding (csrc/kernels/decode_spec.hip): T rows per sequence; the last int is dt as above
     "kca_spec_prep": [P, LL, I, I, I, I, I, I, I, P, P, P, P, P, P, P, LL, LL, LL, P, I, I, I, I, P],
     "kca_spec_attn": [P, LL, P, P, LL, LL, LL, P, P, P, P, LL, P, LL, I, I, I, I, I, I, I, F, P, P, I, I, I, I, P],
+    "kca_prefill_paged_attn": [P, LL, LL, LL, P, LL, LL, LL, P, P, LL, LL, LL, P, P, P, I, I, I, I, I, F, P, P, I, I, I,
+                               I, I, I, P],
     "kca_mm_skinny_set": [I],
     "kca_ln_skinny_gemm": [P, LL, P, P, P, LL, P, P, F, P, P, P, LL, I, I, I, I, P, P],
     "kca_ln_rows": [P, LL, P, P, P, LL, P, P, F, P, I, I, P],
